@@ -5,7 +5,11 @@ A "step" is one pass of the hot path for one main view: build the packed cost vo
 views (sweep kernel), then per-pixel depth selection (argmin kernel).  Inputs are synthetic frames of
 the BASELINE config already resident in HBM when the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--shard frames|views|rows]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--shard frames|views|rows] [--full] [--dump-outputs DIR]
+
+A plain run prints the headline line alone; `--full` adds every other figure (CPU baseline, the other sampler, other cameras, sustained,
+cold and one-call steps, flow and reference-stage blocks; N > 1 the alternative shardings, c4 rows and via-comm).  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy (write_outputs).
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N bench.py ...`; without a launcher
 `--gpus N` starts that launcher itself as a CHILD process (before torch is imported or a GPU touched) and relays its output and
@@ -51,6 +55,53 @@ CONFIGS = {
 DTYPE = {"fixed": "u8", "exact": "f32"}
 CLOCK_RAMP_STEPS = 30   # untimed steps before the warm-up steps of every timed variant (reported as `clock_ramp_steps`)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BYTES = 64 << 20   # --dump-outputs: the most it writes
+DUMP_SEED = 0x5EED0003  # --dump-outputs: the fixed sample of pixels / volume cells where an output is too large to write whole
+DUMP_SAMPLE = 1 << 20   # ... and its size (draws; duplicates are dropped)
+
+
+def scene_views(W, H, V, radius, seed):
+    """synth.make_views(W, H, V, radius=radius, seed=seed), bit for bit, with the V + 1 independent ray casts on a few host threads
+    (numpy releases the GIL inside them): at c3 the serial form is most of a plain run's set-up time"""
+    from concurrent.futures import ThreadPoolExecutor
+
+    import numpy as np
+    from mvs_amd import synth
+    sc = synth.Scene(seed, W / 1920.0)
+    main_cam, side_cams = synth.ring_cameras(V, W, H, radius)
+    centres = [[0.0, 0.0, 0.0]] + [[radius * np.cos(2.0 * np.pi * v / max(V, 1)), radius * np.sin(2.0 * np.pi * v / max(V, 1)), 0.0] for v in range(V)]
+    with ThreadPoolExecutor(max(1, min(len(centres), 8, len(os.sched_getaffinity(0))))) as pool:
+        imgs = list(pool.map(lambda k: sc.render(centres[k], W, H, want_depth=(k == 0)), range(len(centres))))
+    main_img, depth = imgs[0]
+    return main_cam, main_img, side_cams, imgs[1:], depth
+
+
+def write_outputs(path, maps, volume=None):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array (float32 / float64), at most DUMP_BYTES
+    in all.  `maps`: name -> per-pixel array, written whole while they take at most half the budget, else at a fixed seeded sample of
+    pixels (pixel_index.npy holds the flat indices).  `volume`: the packed u32 cost volume as a device tensor, always a fixed seeded
+    sample of its cells (volume_index.npy; the cells as float64, exact).  Same arguments, same inputs, same sample: two builds compare
+    file for file."""
+    import numpy as np
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    out = {}
+    n = next(iter(maps.values())).size
+    if 4 * n * len(maps) > DUMP_BYTES // 2:
+        pix = np.unique(rng.integers(0, n, 2 * DUMP_SAMPLE))
+        out["pixel_index"] = pix.astype(np.float64)
+        maps = {k: np.ascontiguousarray(v).reshape(-1)[pix] for k, v in maps.items()}
+    for k, v in maps.items():
+        out[k] = np.asarray(v).astype(np.float32)   # depth and best cost are f32; plane indices (< 2^24) are exact in f32
+    if volume is not None:
+        import torch
+        cells = np.unique(rng.integers(0, volume.numel(), DUMP_SAMPLE))
+        got = volume.reshape(-1)[torch.as_tensor(cells, device=volume.device)].cpu().numpy().view(np.uint32)
+        out["volume_index"] = cells.astype(np.float64)
+        out["volume_sample"] = got.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_baseline(cfg, main_cam, main_img, side_cams, sides, sampler="fixed"):
@@ -209,6 +260,8 @@ def run_sequence(args, rank, local_rank, world, dist, torch, np, mvs_amd, same_d
     depth = run_frames(seq[CLOCK_RAMP_STEPS + args.warmup:])
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # the depth map of this rank's last main frame (the pinned buffers are reused below)
+        write_outputs(args.dump_outputs, {"depth": np.array(depth)})
     ms_sum, launches = ctx.profile_read(reset=True)
     shape = ctx.plan_shape()
     onecall_ms = None
@@ -501,7 +554,7 @@ def run_via_comm(args, same_device):
     W, H, D, V = cfg
     P = W * H
     if args.data == "scene":
-        main_cam, main_img, side_cams, sides, gt = synth.make_views(W, H, V, radius=0.15, seed=synth.SEED_SCENE)
+        main_cam, main_img, side_cams, sides, gt = scene_views(W, H, V, 0.15, synth.SEED_SCENE)
     else:
         main_cam, main_img, side_cams, sides = synth.noise_views(W, H, V, seed=synth.SEED_NOISE)
         gt = None
@@ -542,6 +595,9 @@ def run_via_comm(args, same_device):
                 crc = zlib.crc32(np.ascontiguousarray(depth).tobytes())
                 if crc != crc1:
                     raise SystemExit("via-comm %s: depth crc %08x, the single-GPU sweep of the same view %08x" % (mode, crc, crc1))
+                if mode == "rows" and args.dump_outputs:   # the headline's mode: what its last call left on GPU 0
+                    d_l, c_l = comm.fetch(want_cost=True)
+                    write_outputs(args.dump_outputs, {"depth": d_l, "cost": c_l})
                 ring = (N - 1) / N
                 results[mode] = {"ms_per_step": dt / args.steps * 1e3, "samples_per_s": float(P) * D * V / (dt / args.steps), "depth_crc32": crc,
                                  "bytes_between_gpus_per_step": (8.0 * P * ring if mode == "rows" else
@@ -550,24 +606,25 @@ def run_via_comm(args, same_device):
                 if mode == "rows":
                     raise
                 results[mode] = {"error": str(e)}
-        # rows mode once more with two calls in flight (mvs_comm_run_async / mvs_comm_wait): the bands of call k travel to rank 0 beside the sweep
-        # of call k + 1; the timed region ends when every call has been waited for
-        comm.set_mode("rows")
-        for _ in range(CLOCK_RAMP_STEPS + args.warmup):
+        if not args.no_extras:
+            # rows mode once more with two calls in flight (mvs_comm_run_async / mvs_comm_wait): the bands of call k travel to rank 0 beside the sweep
+            # of call k + 1; the timed region ends when every call has been waited for
+            comm.set_mode("rows")
+            for _ in range(CLOCK_RAMP_STEPS + args.warmup):
+                comm.run_async()
+                comm.wait()
+            t0 = time.perf_counter()
             comm.run_async()
+            for _ in range(args.steps - 1):
+                comm.run_async()
+                comm.wait()
             comm.wait()
-        t0 = time.perf_counter()
-        comm.run_async()
-        for _ in range(args.steps - 1):
-            comm.run_async()
-            comm.wait()
-        comm.wait()
-        dt = time.perf_counter() - t0
-        crc = zlib.crc32(np.ascontiguousarray(comm.fetch(want_cost=False)).tobytes())
-        if crc != crc1:
-            raise SystemExit("via-comm rows_async: depth crc %08x, the single-GPU sweep of the same view %08x" % (crc, crc1))
-        results["rows_async"] = {"ms_per_step": dt / args.steps * 1e3, "samples_per_s": float(P) * D * V / (dt / args.steps), "depth_crc32": crc,
-                                 "bytes_between_gpus_per_step": 8.0 * P * (N - 1) / N, "in_flight": 2}
+            dt = time.perf_counter() - t0
+            crc = zlib.crc32(np.ascontiguousarray(comm.fetch(want_cost=False)).tobytes())
+            if crc != crc1:
+                raise SystemExit("via-comm rows_async: depth crc %08x, the single-GPU sweep of the same view %08x" % (crc, crc1))
+            results["rows_async"] = {"ms_per_step": dt / args.steps * 1e3, "samples_per_s": float(P) * D * V / (dt / args.steps), "depth_crc32": crc,
+                                     "bytes_between_gpus_per_step": 8.0 * P * (N - 1) / N, "in_flight": 2}
         peer_access, comm_devices, comm_note = comm.peer_access(), comm.devices(), comm.note()
     rows = results["rows"]
     rows_alg_bytes = float(min(band, H)) * W * (V + 8.0 * D + 9.0)   # rank 0's band, SURVEY 8(d)
@@ -600,7 +657,7 @@ def via_comm_child(args, timeout_s):
     CHILD process (a fresh process: no torch.distributed, its own contexts) with a time limit, so that a failure there cannot cost the
     line.  Returns the child's parsed line, or {"error": ...}."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--via-comm", "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
+    cmd = [sys.executable, os.path.abspath(__file__), "--via-comm", "--full", "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--config", args.config, "--sampler", args.sampler, "--data", args.data, "--plane-groups", str(args.plane_groups)]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "MASTER_ADDR", "MASTER_PORT",
                                                               "TORCHELASTIC_RUN_ID", "OMP_NUM_THREADS")}
@@ -790,7 +847,16 @@ def main():
     ap.add_argument("--via-comm-timeout", type=float, default=240.0, help="seconds the launcher's rank 0 waits for its --via-comm child before giving up on the via_comm block")
     ap.add_argument("--data", default="scene", choices=["scene", "noise"],
                     help="scene: analytic surface ray-cast per view (SURVEY 8d, seed 0x5EED0001); noise: i.i.d. u8 (seed 0x5EED0002)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: N = 1 the CPU baseline, the other sampler, general and translated cameras, the "
+                         "sustained run, the cold and one-call steps, the flow and reference-stage blocks; N > 1 the alternative shardings, c4 rows "
+                         "and the via-comm child.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (depth, best cost, plane index; a fixed sample of the volume) "
+                         "as DIR/<name>.npy in float32 / float64, at most 64 MB")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline alone
+        args.no_extras = args.no_cpu_baseline = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -845,7 +911,7 @@ def main():
     radius = 0.15
     seed_off = rank if shard == "frames" else 0
     if args.data == "scene":
-        main_cam, main_img, side_cams, sides, gt = synth.make_views(W, H, V, radius=radius, seed=synth.SEED_SCENE + seed_off)
+        main_cam, main_img, side_cams, sides, gt = scene_views(W, H, V, radius, synth.SEED_SCENE + seed_off)
     else:
         main_cam, main_img, side_cams, sides = synth.noise_views(W, H, V, seed=synth.SEED_NOISE + seed_off)
         gt = None
@@ -989,6 +1055,12 @@ def main():
                 "collective_bytes_per_rank": coll_bytes, "depth": depth, "crc": crc, "separate": launches[mvs_amd.MVS_K_ARGMIN] > 0}
 
     primary = timed(shard, args.collective if shard == "views" else None)
+    if args.dump_outputs and rank == 0:   # before anything else runs on these buffers
+        if world == 1:
+            d_l, c_l, i_l, _ = ctx.sweep_fetch()
+            write_outputs(args.dump_outputs, {"depth": d_l, "cost": c_l, "plane_index": i_l}, vol_t)
+        else:   # rank 0 holds the whole view's depth map (rows: gathered; views: selected from the summed volume)
+            write_outputs(args.dump_outputs, {"depth": primary["depth"]})
     alternatives = None
     if world > 1 and args.shard is None and not args.no_extras:
         alternatives = {}

@@ -25,7 +25,7 @@ def _bench(extra, world):
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                 "--master-port", str(port)]
     cmd += [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--config", "c1", "--steps", "2", "--warmup", "1",
-            "--no-cpu-baseline"] + (["--no-extras"] if "--with-extras" not in extra else []) + [e for e in extra if e != "--with-extras"]
+            "--no-cpu-baseline"] + (["--no-extras"] if "--with-extras" not in extra else ["--full"]) + [e for e in extra if e != "--with-extras"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
@@ -114,11 +114,35 @@ def test_bench_line_contract_and_two_rank_shardings():
             assert 0 < f["recovered_fraction"] < 1 and f["device_ms"] > 0
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) prints the headline alone; --dump-outputs writes what the last timed step returned, the same in every run"""
+    import zlib
+
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        got = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert out.returncode == 0 and len(got) == 1, out.stderr[-2000:]
+        lines.append(json.loads(got[0]))
+    rec = lines[0]
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True and rec["dtype"] == "u8" and rec["depth_check"] is True
+    for key in ("cpu_baseline", "exact_sampler", "sustained", "cold_step", "one_call_mvs_sweep", "flow", "reference_stage", "general_camera_path"):
+        assert key not in rec, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["cost.npy", "depth.npy", "plane_index.npy", "volume_index.npy", "volume_sample.npy"]
+    depth = np.load(tmp_path / "a" / "depth.npy")
+    assert depth.dtype == np.float32 and depth.shape == (480, 640) and zlib.crc32(depth.tobytes()) == rec["depth_crc32"]
+    for n in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+
+
 def test_via_comm_line():
     """bench.py --via-comm: ONE process drives N GPUs through mvs_comm_set_* / mvs_comm_run (here: 3 ranks on the one GPU, loopback
     collectives, labelled as the test hook it is); the line keeps the contract and every mode reproduces the single-GPU depth map"""
     env = dict(os.environ, MVS_BENCH_SAME_DEVICE="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--via-comm", "--gpus", "3", "--config", "c1", "--steps", "3", "--warmup", "1"], env=env, cwd=ROOT,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--via-comm", "--full", "--gpus", "3", "--config", "c1", "--steps", "3", "--warmup", "1"], env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]

@@ -117,7 +117,7 @@ def test_bench_over_rccl_matches_single_gpu():
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", str(n), "--config", "c1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           os.path.join(root, "bench.py"), "--gpus", str(n), "--config", "c1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-3000:]
