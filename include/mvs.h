@@ -272,6 +272,36 @@ int mvs_sweep_batch_async(mvs_ctx *ctx, int nmain, const int *main_slots, const 
                           const float *side_cams, int nplanes, float z_lo, float z_hi, float *depth_out, float *cost_out);
 int mvs_sweep_batch_wait(mvs_ctx *ctx);
 
+/* ---- depth store + fusion: depth maps of a sequence -> one multi-view-consistent oriented point cloud (csrc/fuse.hip) ----
+ * The store keeps depth maps in the library's convention (main-camera NDC z, 1.0 = empty: a sweep's result, or mvs_depth of a mesh) with
+ * their best costs and cameras in HBM.  Life cycle as the frame store's: mvs_depth_store sizes it (1..8191 slots, re-sizing empties it);
+ * uploads are stream-ordered (host buffers must stay valid until the next synchronising call, e.g. mvs_fuse_depth).  cost may be NULL;
+ * mvs_depth_upload_device(ctx, slot, cam, mvs_sweep_depth_device(ctx), mvs_sweep_cost_device(ctx)) stores a sweep's result device to device.
+ * mvs_fuse_depth: for every pixel (row, col) of ref_slot with depth z, all in f32, one rounding per operation, no contraction:
+ *   1 valid: -1 < z < 1 (and cost <= max_cost when max_cost is finite)
+ *   2 X = h.xyz / h.w with h = P_r^-1 (xn, yn, z, 1), xn / yn the sweep's pixel centres; w_r = (P_r (X, 1)).w must be > 0
+ *   3 neighbour j (listed order): q = P_j (X, 1), q.w > 0; u = (q.x/q.w + 1) W/2 - 1/2, v = (1 - q.y/q.w) H/2 - 1/2; pixel
+ *     (floor(v + 1/2), floor(u + 1/2)) in the frame and valid in j; X_j = its back-projection through P_j^-1; s = P_r (X_j, 1), s.w > 0;
+ *     j agrees when the reprojection (u_r, v_r) of X_j lies within max_reproj_px of (col, row) and |s.w - w_r| / w_r <= max_rel_depth
+ *   4 kept when at least min_consistent neighbours agree; point = (X + agreeing X_j, summed in listed order) / count, w = 1
+ *   5 normal from the reference map alone: tangents along columns and rows from the valid 4-neighbours whose linear depth is within
+ *     max_rel_depth of w_r (central difference, else one-sided, else none: the pixel is dropped); n = normalize(t_col x t_row), flipped
+ *     to face the camera centre (outward, as mvs_poisson_surface needs)
+ * Rows (x, y, z, 1, nx, ny, nz) in ascending pixel index, the same from run to run.  mvs_fuse_depth synchronises and returns the row count;
+ * out_points7 (nullable, room for H*W rows) receives the rows; they stay in HBM for mvs_fuse_points_device until the next mvs_fuse_depth.
+ * Errors: MVS_EINVAL for a NULL ctx, a slot outside the store, nneighbours outside 0..16, a neighbour equal to ref_slot, min_consistent
+ * outside 0..nneighbours, a negative (or NaN) threshold, a singular camera; MVS_ESTATE for an unfilled slot, or a finite max_cost when a
+ * slot involved was stored without cost.  max_cost = INFINITY: costs are not read. */
+int mvs_depth_store(mvs_ctx *ctx, int capacity);
+int mvs_depth_upload(mvs_ctx *ctx, int slot, const float cam[16], const float *depth_hw, const float *cost_hw /* nullable */);
+int mvs_depth_upload_device(mvs_ctx *ctx, int slot, const float cam[16], const void *depth_dev, const void *cost_dev /* nullable */);
+int mvs_fuse_depth(mvs_ctx *ctx, int ref_slot, int nneighbours, const int *neighbour_slots, int min_consistent, float max_reproj_px,
+                   float max_rel_depth, float max_cost, float *out_points7 /* nullable: H*W*7 */, int *out_count);
+void *mvs_fuse_points_device(mvs_ctx *ctx); /* rows of the last mvs_fuse_depth, in HBM; NULL before the first */
+/* diagnostic: the slot's matrices as the kernels use them: out[0..15] = P, out[16..31] = P^-1 (inverted in double, rounded once),
+ * out[32..35] = camera centre (x, y, z, 1): the null vector of P's rows x, y, w, dehomogenised in double, rounded once */
+int mvs_depth_slot_matrices(const mvs_ctx *ctx, int slot, float out[36]);
+
 /* ---- one main view on several GPUs of one node (SURVEY.md section 8b "multi-GPU", 8e, north_star) -----------------------------
  * A communicator owns one context per listed device and one RCCL communicator across them (librccl is loaded when the first
  * communicator is created; the library has no link dependency on it).  mvs_sweep_sharded runs ONE main view on all of them, one host
@@ -351,6 +381,7 @@ int mvs_comm_device(const mvs_comm *comm, int rank);
 #define MVS_K_RASTER 3
 #define MVS_K_PROJECT 4
 #define MVS_K_FLOW 5
+#define MVS_K_FUSE 6 /* mvs_fuse_depth: count pass, scan, row pass */
 #define MVS_K_COUNT 8
 int mvs_profile_enable(mvs_ctx *ctx, int on);
 /* synchronises, then returns summed elapsed ms and launch count per kernel class since the last reset */

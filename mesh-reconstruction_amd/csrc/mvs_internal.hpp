@@ -149,6 +149,17 @@ struct mvs_ctx {
     FlowLane lanes[kFlowLanes];
     std::vector<hipEvent_t> lane_events;  // 2 per side view: inputs ready, flow done
 
+    // depth store (fuse.hip: mvs_depth_store / mvs_depth_upload / mvs_fuse_depth): per slot an H*W f32 depth map, an H*W f32 cost map
+    // and the camera's matrices as the fusion kernels use them (host copy; they travel as kernel arguments)
+    struct DepthSlot {
+        bool have = false, have_cost = false;
+        float P[16], Pi[16], C[4];
+    };
+    mvs::DevBuf dstore_depth, dstore_cost;
+    std::vector<DepthSlot> dstore;
+    mvs::DevBuf fuse_rows, fuse_counts, fuse_scan;  // rows of the last mvs_fuse_depth; per-segment keep counts and their offsets; scan scratch
+    bool fuse_have_rows = false;
+
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;
     std::vector<mvs::ProfileSlot> slots;

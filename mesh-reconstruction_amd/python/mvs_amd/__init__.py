@@ -25,7 +25,7 @@ MVS_SHARD_ROWS, MVS_SHARD_VIEWS, MVS_SHARD_VIEWS_SCATTER = 0, 1, 2
 SHARD_MODES = {"rows": 0, "views": 1, "views_scatter": 2}
 MVS_SAMPLER_FIXED, MVS_SAMPLER_EXACT_F32 = 0, 1
 SAMPLERS = {"fixed": MVS_SAMPLER_FIXED, "exact": MVS_SAMPLER_EXACT_F32}
-MVS_K_SWEEP, MVS_K_ARGMIN, MVS_K_PLAN, MVS_K_RASTER, MVS_K_PROJECT, MVS_K_FLOW = 0, 1, 2, 3, 4, 5
+MVS_K_SWEEP, MVS_K_ARGMIN, MVS_K_PLAN, MVS_K_RASTER, MVS_K_PROJECT, MVS_K_FLOW, MVS_K_FUSE = 0, 1, 2, 3, 4, 5, 6
 MVS_K_COUNT = 8
 BACKGROUND_DEPTH = np.float32(1.0)
 
@@ -80,6 +80,12 @@ ABI = [
     ("mvs_sweep_batch", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, C.c_float, C.c_float, _vp, _vp]),
     ("mvs_sweep_batch_async", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, C.c_float, C.c_float, _vp, _vp]),
     ("mvs_sweep_batch_wait", _i, [_vp]),
+    ("mvs_depth_store", _i, [_vp, _i]),
+    ("mvs_depth_upload", _i, [_vp, _i, _fp, _fp, _fp]),
+    ("mvs_depth_upload_device", _i, [_vp, _i, _fp, _vp, _vp]),
+    ("mvs_fuse_depth", _i, [_vp, _i, _i, _i32p, _i, _f, _f, _f, _fp, C.POINTER(_i)]),
+    ("mvs_fuse_points_device", _vp, [_vp]),
+    ("mvs_depth_slot_matrices", _i, [_vp, _i, _fp]),
     ("mvs_sweep_argmin", _i, [_vp]),
     ("mvs_sweep_refine_depth", _i, [_vp]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
@@ -698,6 +704,52 @@ class Context:
                                              cost.ctypes.data_as(C.c_void_p) if want_cost else None))
         self._store_keep = {}
         return (depth, cost) if want_cost else depth
+
+    # ---- depth store + fusion ---------------------------------------------------------------------
+    def depth_store(self, capacity):
+        """mvs_depth_store: capacity slots of H*W depth + cost + camera; re-sizing empties the store"""
+        self._check(self.lib.mvs_depth_store(self.h, int(capacity)))
+        self._depth_keep = {}
+
+    def depth_upload(self, slot, cam, depth, cost=None):
+        """mvs_depth_upload: depth [H,W] f32 NDC z (1.0 = empty), cost [H,W] f32 or None (asynchronous: the arrays are kept alive here
+        until the next fuse_depth)"""
+        c = _f32(cam, (4, 4))
+        d = _f32(depth, (self.H, self.W))
+        k = _f32(cost, (self.H, self.W)) if cost is not None else None
+        self.__dict__.setdefault("_depth_keep", {})[int(slot)] = (c, d, k)
+        self._check(self.lib.mvs_depth_upload(self.h, int(slot), _ptr(c, _fp), _ptr(d, _fp), _ptr(k, _fp) if k is not None else None))
+
+    def depth_upload_device(self, slot, cam, depth_ptr, cost_ptr=None):
+        """mvs_depth_upload_device: device addresses of H*W f32 depth (and cost), e.g. sweep_result_pointers() (stream-ordered)"""
+        c = _f32(cam, (4, 4))
+        self._check(self.lib.mvs_depth_upload_device(self.h, int(slot), _ptr(c, _fp), C.c_void_p(int(depth_ptr)),
+                                                     C.c_void_p(int(cost_ptr)) if cost_ptr else None))
+
+    def fuse_depth(self, ref_slot, neighbour_slots, min_consistent=2, max_reproj_px=1.0, max_rel_depth=0.01, max_cost=float("inf"), copy=True):
+        """mvs_fuse_depth -> (N, 7) float32 rows (x, y, z, 1, nx, ny, nz) in ascending pixel index.  copy=False: a view of the context's
+        reusable output buffer (the one process_frame uses), valid until the next call that writes it"""
+        nb = np.ascontiguousarray(np.asarray(list(neighbour_slots) if len(neighbour_slots) else [0], dtype=np.int32))
+        if getattr(self, "_pf_out", None) is None:
+            self._pf_out = np.zeros((self.H * self.W, 7), np.float32)
+        out = self._pf_out
+        n = C.c_int(0)
+        try:
+            self._check(self.lib.mvs_fuse_depth(self.h, int(ref_slot), len(neighbour_slots), _ptr(nb, _i32p), int(min_consistent), float(max_reproj_px),
+                                                float(max_rel_depth), float(max_cost), _ptr(out, _fp), C.byref(n)))
+        finally:
+            self._depth_keep = {}
+        return out[:n.value].copy() if copy else out[:n.value]
+
+    def fuse_points_device(self):
+        """device address of the rows of the last fuse_depth (0 before the first)"""
+        return self.lib.mvs_fuse_points_device(self.h) or 0
+
+    def depth_slot_matrices(self, slot):
+        """mvs_depth_slot_matrices -> (P [4,4], P^-1 [4,4], centre [4]) as the fusion kernels use them"""
+        m = np.empty(36, np.float32)
+        self._check(self.lib.mvs_depth_slot_matrices(self.h, int(slot), _ptr(m, _fp)))
+        return m[:16].reshape(4, 4).copy(), m[16:32].reshape(4, 4).copy(), m[32:].copy()
 
     def depth_device_array(self):
         """zero-copy [H, W] f32 view of the device depth map for torch.as_tensor(..., device='cuda') (valid until the
