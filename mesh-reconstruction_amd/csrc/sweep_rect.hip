@@ -27,9 +27,11 @@
 // buffer_load_dwordx4 ... lds (dense rows of RS quads, 1 KiB = 64 lanes x 16 B per instruction, per-lane source offsets fixed for the
 // launch), one region ahead of the one being sampled; s_waitcnt vmcnt(0) + one s_barrier per region make every wavefront's part
 // visible and free the slot the next copy goes to.  The X / Y records of the coming regions travel through vector registers (lane l =
-// dword l, v_readlane when the region's turn comes).  The sample loop is one inline-asm statement per plane (M0-based
-// ds_read_addtid_b32, v_dot4_u32_u8, v_sad_u16; planes that are not FULL run it with EXEC = 0): the compiler would order every ds_read
-// behind ALL pending LDS copies, and a per-plane branch costs more scalar instructions than the plane's arithmetic.
+// dword l, v_readlane when the region's turn comes).  A region's sampling is inline asm in two shapes, chosen by one wave-uniform test
+// per region: CLEAN (all four planes FULL) is one straight-line statement for the four planes, the next plane's reads in flight behind
+// the current plane's arithmetic; otherwise one statement per plane (M0-based ds_read_addtid_b32, v_dot4_u32_u8, v_sad_u16; border
+// planes under EXEC masks, planes with nothing in frame branched over) plus the block for failed certificates.  Not compiler code: the
+// compiler would order every ds_read behind ALL pending LDS copies.
 // What bounds it (profiles/r03): vector-instruction issue.  Measured and rejected: a second region of look-ahead
 // with counted waits (three slots, records through an LDS ring; +10 %), row-wise copies (+8 %), copies that all hit in L2 (no change).
 #include "sweep_shared.hpp"
@@ -521,140 +523,194 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
             // per plane: what is out of frame although the certificates hold (0: nothing -- with no flag in the field that is a FULL plane)
             const uint32_t xmasks = rdl(x0r, 7), ymasks = rdl(y0r, 4);
             const uint32_t anymask = xmasks | ymasks;
-            if (__builtin_expect(anymask != 0u, 0)) {
-#pragma unroll
-                for (int k = 0; k < RX_KW; k++)
-                    if (((anymask >> (8 * k)) & 0xffu) && !(fld[k] & 0xc000u)) spacc += 1u << (8 * k);  // this view's count does not go to every cell of the plane
-            }
-            // One asm statement per plane: LDS base in M0 (ds_read_addtid_b32: M0 + offset + 4 lane, no address register), weight word in
-            // an SGPR, 8 reads, 8 v_dot4, 8 v_sad_u16 (all dot products before all differences: a v_sad right behind the v_dot4 it
-            // consumes costs wait states).  A plane whose certificate failed (flag bits in the field) reads as well (somewhere in or past
-            // the LDS: harmless) and runs its vector instructions with EXEC = 0; the block below does those planes.  The s_and between
-            // the write of M0 and the first read is the wait state that pair needs.
-            // A plane of a tile at the border of the side view (its byte of `am` is not 0) branches to the tail INSIDE the statement --
-            // same registers, no second shape for the register allocator: EXEC = the lanes in frame (x byte: n | side << 7, n = 64:
-            // none), then row by row EXEC = that or nothing (y byte: the rows that are out), each cell that gets the sample counting it
-            // itself (+ 1 << 24).  The tail costs the planes that are FULL one taken s_branch.
-#define RX_ROW_TAIL(j)                                                                                                   \
-    "s_bitcmp0_b32 %[ym], %[yb" #j "]\n\ts_cselect_b64 exec, vcc, 0\n\tv_add_u32 %[a" #j "], 0x1000000, %[a" #j "]\n\t" \
-    "v_sad_u16 %[a" #j "], %[q" #j "], %[i" #j "], %[a" #j "]\n\t"
-#pragma unroll
-            for (int k = 0; k < RX_KW; k++) {   // (experiment 512 -- every plane sampled twice: the work of 8 planes per wavefront, DESIGN A.5b -- has served and is gone: its
-                                                 // run-time trip count no longer compiles with the immediates below)
+            const uint32_t clean = special | anymask;  // 0: CLEAN
+            {
+                // CLEAN region (every plane FULL: certified, every pixel in frame): one straight-line statement for the four planes,
+                // no EXEC write, no branch.  The reads of plane k + 1 follow the v_sad_u16s of plane k row by row into the same 8
+                // registers (row j's read behind row j's sad), so they are in flight while plane k finishes; plane k + 1's v_dot4s then
+                // wait for their pair of rows with a counted lgkmcnt (LDS reads return in order).  The lgkmcnt(0) in front: a scalar
+                // load the compiler left in flight would make the counted waits a lower bound only.  Every v_sad reads a v_dot4 result
+                // 8 VALU instructions after it was written (the pair needs wait states the compiler does not insert inside asm);
+                // the M0 write of the first plane gets its wait state from the s_nop, the later ones from the v_sad in front of the read.
+#define RX_RD(j) "ds_read_addtid_b32 %[q" #j "] offset:%[o" #j "]\n\t"
+#define RX_DOT(j, k) "v_dot4_u32_u8 %[q" #j "], %[q" #j "], %[w" #k "], 0\n\t"
+#define RX_SAD(j, k) "v_sad_u16 %[a" #j #k "], %[q" #j "], %[i" #j "], %[a" #j #k "]\n\t"
+#define RX_DOTS(k)                                                                                                        \
+    "s_waitcnt lgkmcnt(6)\n\t" RX_DOT(0, k) RX_DOT(1, k) "s_waitcnt lgkmcnt(4)\n\t" RX_DOT(2, k) RX_DOT(3, k)                \
+    "s_waitcnt lgkmcnt(2)\n\t" RX_DOT(4, k) RX_DOT(5, k) "s_waitcnt lgkmcnt(0)\n\t" RX_DOT(6, k) RX_DOT(7, k)
+#define RX_PLANE(k, kn)                                                                                                   \
+    RX_DOTS(k) "s_add_u32 m0, %[slot], %[f" #kn "]\n\t"                                                                  \
+    RX_SAD(0, k) RX_RD(0) RX_SAD(1, k) RX_RD(1) RX_SAD(2, k) RX_RD(2) RX_SAD(3, k) RX_RD(3)                                  \
+    RX_SAD(4, k) RX_RD(4) RX_SAD(5, k) RX_RD(5) RX_SAD(6, k) RX_RD(6) RX_SAD(7, k) RX_RD(7)
+#define RX_ACC(k)                                                                                                         \
+    [a0##k] "+v"(acc[0][k]), [a1##k] "+v"(acc[1][k]), [a2##k] "+v"(acc[2][k]), [a3##k] "+v"(acc[3][k]),                   \
+    [a4##k] "+v"(acc[4][k]), [a5##k] "+v"(acc[5][k]), [a6##k] "+v"(acc[6][k]), [a7##k] "+v"(acc[7][k])
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
-                asm volatile("s_add_u32 m0, %[slot], %[fld]\n\t"
-                             "s_and_b32 vcc_lo, %[fld], 0xc000\n\t"
-                             "ds_read_addtid_b32 %[q0] offset:%[o0]\n\tds_read_addtid_b32 %[q1] offset:%[o1]\n\tds_read_addtid_b32 %[q2] offset:%[o2]\n\tds_read_addtid_b32 %[q3] offset:%[o3]\n\t"
-                             "ds_read_addtid_b32 %[q4] offset:%[o4]\n\tds_read_addtid_b32 %[q5] offset:%[o5]\n\tds_read_addtid_b32 %[q6] offset:%[o6]\n\tds_read_addtid_b32 %[q7] offset:%[o7]\n\t"
-                             "s_cselect_b64 exec, 0, -1\n\t"
-                             "s_bfe_u32 vcc_lo, %[am], %[kb]\n\t"  // this plane's byte of the masks: SCC = not 0
-                             "s_cbranch_scc1 1f\n\t"
+                asm volatile("s_cmp_lg_u32 %[cl], 0\n\t"
+                             "s_cbranch_scc1 9f\n\t"
                              "s_waitcnt lgkmcnt(0)\n\t"
-                             "v_dot4_u32_u8 %[q0], %[q0], %[w], 0\n\tv_dot4_u32_u8 %[q1], %[q1], %[w], 0\n\tv_dot4_u32_u8 %[q2], %[q2], %[w], 0\n\tv_dot4_u32_u8 %[q3], %[q3], %[w], 0\n\t"
-                             "v_dot4_u32_u8 %[q4], %[q4], %[w], 0\n\tv_dot4_u32_u8 %[q5], %[q5], %[w], 0\n\tv_dot4_u32_u8 %[q6], %[q6], %[w], 0\n\tv_dot4_u32_u8 %[q7], %[q7], %[w], 0\n\t"
-                             "v_sad_u16 %[a0], %[q0], %[i0], %[a0]\n\tv_sad_u16 %[a1], %[q1], %[i1], %[a1]\n\tv_sad_u16 %[a2], %[q2], %[i2], %[a2]\n\tv_sad_u16 %[a3], %[q3], %[i3], %[a3]\n\t"
-                             "v_sad_u16 %[a4], %[q4], %[i4], %[a4]\n\tv_sad_u16 %[a5], %[q5], %[i5], %[a5]\n\tv_sad_u16 %[a6], %[q6], %[i6], %[a6]\n\tv_sad_u16 %[a7], %[q7], %[i7], %[a7]\n\t"
-                             "2:\n\t"
-                             "s_mov_b64 exec, -1\n\t"
-                             "s_branch 9f\n\t"
-                             // ---- the tail: lanes in frame from the x byte
-                             "1:\n\t"
-                             "s_bfe_u32 vcc_lo, %[xm], %[nb]\n\t"        // n (6 bits)
-                             "s_bitcmp1_b32 %[xm], %[sb]\n\t"            // side
-                             "s_cbranch_scc1 3f\n\t"
-                             "s_lshl_b64 exec, exec, vcc_lo\n\t"         // the first n lanes are out
-                             "s_branch 4f\n\t"
-                             "3:\n\t"
-                             "s_lshr_b64 exec, exec, vcc_lo\n\t"         // the last n lanes are out
-                             "4:\n\t"
-                             "s_bitcmp1_b32 %[xm], %[eb]\n\t"            // n = 64: nothing in frame
-                             "s_cselect_b64 exec, 0, exec\n\t"
-                             "s_mov_b64 vcc, exec\n\t"
-                             "s_waitcnt lgkmcnt(0)\n\t"
-                             "v_dot4_u32_u8 %[q0], %[q0], %[w], 0\n\tv_dot4_u32_u8 %[q1], %[q1], %[w], 0\n\tv_dot4_u32_u8 %[q2], %[q2], %[w], 0\n\tv_dot4_u32_u8 %[q3], %[q3], %[w], 0\n\t"
-                             "v_dot4_u32_u8 %[q4], %[q4], %[w], 0\n\tv_dot4_u32_u8 %[q5], %[q5], %[w], 0\n\tv_dot4_u32_u8 %[q6], %[q6], %[w], 0\n\tv_dot4_u32_u8 %[q7], %[q7], %[w], 0\n\t"
-                             RX_ROW_TAIL(0) RX_ROW_TAIL(1) RX_ROW_TAIL(2) RX_ROW_TAIL(3) RX_ROW_TAIL(4) RX_ROW_TAIL(5) RX_ROW_TAIL(6) RX_ROW_TAIL(7)
-                             "s_branch 2b\n\t"
+                             "s_add_u32 m0, %[slot], %[f0]\n\t"
+                             "s_nop 0\n\t"
+                             RX_RD(0) RX_RD(1) RX_RD(2) RX_RD(3) RX_RD(4) RX_RD(5) RX_RD(6) RX_RD(7)
+                             RX_PLANE(0, 1) RX_PLANE(1, 2) RX_PLANE(2, 3)
+                             RX_DOTS(3)
+                             RX_SAD(0, 3) RX_SAD(1, 3) RX_SAD(2, 3) RX_SAD(3, 3) RX_SAD(4, 3) RX_SAD(5, 3) RX_SAD(6, 3) RX_SAD(7, 3)
                              "9:"
                              : [q0] "=&v"(qd[0][0]), [q1] "=&v"(qd[0][1]), [q2] "=&v"(qd[0][2]), [q3] "=&v"(qd[0][3]), [q4] "=&v"(qd[0][4]), [q5] "=&v"(qd[0][5]), [q6] "=&v"(qd[0][6]), [q7] "=&v"(qd[0][7]),
-                               [a0] "+v"(acc[0][k]), [a1] "+v"(acc[1][k]), [a2] "+v"(acc[2][k]), [a3] "+v"(acc[3][k]), [a4] "+v"(acc[4][k]), [a5] "+v"(acc[5][k]), [a6] "+v"(acc[6][k]), [a7] "+v"(acc[7][k])
-                             : [slot] "s"(slot_byte), [fld] "s"(fld[k]), [w] "s"(we[k]), [am] "s"(anymask), [xm] "s"(xmasks), [ym] "s"(ymasks),
+                               RX_ACC(0), RX_ACC(1), RX_ACC(2), RX_ACC(3)
+                             : [cl] "s"(clean), [slot] "s"(slot_byte), [f0] "s"(fld[0]), [f1] "s"(fld[1]), [f2] "s"(fld[2]), [f3] "s"(fld[3]),
+                               [w0] "s"(we[0]), [w1] "s"(we[1]), [w2] "s"(we[2]), [w3] "s"(we[3]),
                                [i0] "v"(Im255[0]), [i1] "v"(Im255[1]), [i2] "v"(Im255[2]), [i3] "v"(Im255[3]), [i4] "v"(Im255[4]), [i5] "v"(Im255[5]), [i6] "v"(Im255[6]), [i7] "v"(Im255[7]),
-                               [o0] "n"(0), [o1] "n"(RS * 4), [o2] "n"(RS * 8), [o3] "n"(RS * 12), [o4] "n"(RS * 16), [o5] "n"(RS * 20), [o6] "n"(RS * 24), [o7] "n"(RS * 28),
-                               [kb] "n"(8 * k | (8 << 16)), [nb] "n"(8 * k | (6 << 16)), [sb] "n"(8 * k + 7), [eb] "n"(8 * k + 6),
-                               [yb0] "n"(8 * k + 0), [yb1] "n"(8 * k + 1), [yb2] "n"(8 * k + 2), [yb3] "n"(8 * k + 3), [yb4] "n"(8 * k + 4), [yb5] "n"(8 * k + 5), [yb6] "n"(8 * k + 6), [yb7] "n"(8 * k + 7)
-                             : "m0", "scc", "vcc");
+                               [o0] "n"(0), [o1] "n"(RS * 4), [o2] "n"(RS * 8), [o3] "n"(RS * 12), [o4] "n"(RS * 16), [o5] "n"(RS * 20), [o6] "n"(RS * 24), [o7] "n"(RS * 28)
+                             : "m0", "scc");
 #pragma clang diagnostic pop
+#undef RX_ACC
+#undef RX_PLANE
+#undef RX_DOTS
+#undef RX_SAD
+#undef RX_DOT
+#undef RX_RD
             }
-#undef RX_ROW_TAIL
-            // the planes whose certificate failed (a rounding boundary inside the tile), or whose offsets did not fit the record
-            if (special) {
-                uintptr_t coldp = (uintptr_t)a.cold;
-                asm volatile("" : "+s"(coldp));  // not loop-invariant for the optimiser: fetched here, not held in SGPRs over the loop
-                const int dpad = RX_COLD(coldp, int, dpad);
-                const cu32 xt = as_const<cu32>(RX_COLD(coldp, const uint32_t *, xt) + ((size_t)tx * a.V + v) * dpad + chunk * RX_PC + wave * RX_KW);
-                const cu32 yt = as_const<cu32>(RX_COLD(coldp, const uint32_t *, yt) + ((size_t)ty * a.V + v) * dpad + chunk * RX_PC + wave * RX_KW);
-                const uint32_t xsx = rdl(x0r, 6), yn = rdl(y0r, 3);
-                const int x0 = (int)((xsx & 0xffffu) >> 2), y0 = (int)((yn >> 8) & 0x3fffu);
-                const bool staged = (xsx >> 16) != 0u && (yn & 0xffu) != 0u;
+            if (__builtin_expect(clean != 0u, 0)) {
+                if (__builtin_expect(anymask != 0u, 0)) {
+#pragma unroll
+                    for (int k = 0; k < RX_KW; k++)
+                        if (((anymask >> (8 * k)) & 0xffu) && !(fld[k] & 0xc000u)) spacc += 1u << (8 * k);  // this view's count does not go to every cell of the plane
+                }
+                // One asm statement per plane: LDS base in M0 (ds_read_addtid_b32: M0 + offset + 4 lane, no address register), weight word in
+                // an SGPR, 8 reads, 8 v_dot4, 8 v_sad_u16 (all dot products before all differences: a v_sad right behind the v_dot4 it
+                // consumes costs wait states).  A plane whose certificate failed (flag bits in the field) reads as well (somewhere in or past
+                // the LDS: harmless) and runs its vector instructions with EXEC = 0; the block below does those planes.  The s_and between
+                // the write of M0 and the first read is the wait state that pair needs.
+                // A plane of a tile at the border of the side view (its byte of `am` is not 0) branches to the tail INSIDE the statement --
+                // same registers, no second shape for the register allocator: EXEC = the lanes in frame (x byte: n | side << 7, n = 64:
+                // none), then row by row EXEC = that or nothing (y byte: the rows that are out), each cell that gets the sample counting it
+                // itself (+ 1 << 24).  The tail costs the planes that are FULL one taken s_branch.
+#define RX_ROW_TAIL(j)                                                                                                   \
+        "s_bitcmp0_b32 %[ym], %[yb" #j "]\n\ts_cselect_b64 exec, vcc, 0\n\tv_add_u32 %[a" #j "], 0x1000000, %[a" #j "]\n\t" \
+        "v_sad_u16 %[a" #j "], %[q" #j "], %[i" #j "], %[a" #j "]\n\t"
 #pragma unroll
                 for (int k = 0; k < RX_KW; k++) {
-                    if (!(fld[k] & 0xc000u)) continue;
-                    spacc += 1u << (8 * k);  // not FULL: this view's count does not go to every cell of the plane
-                    if (!staged) continue;
-                    const uint32_t xe = xt[k], ye = yt[k];
-                    const int nx = (int)((xe >> 20) & 127u), ny = (int)((ye >> 20) & 127u);
-                    if ((xe & ye) & RX_UNIFORM) {
-                        if (nx >= TILE_W || ny >= RX_TILE_H) continue;  // nothing in frame
-                        // a lane range (from the X entry) and a row range (from the Y entry) are in frame: the fast path under a mask,
-                        // the in-frame count per cell
-                        const int tx0 = (int)(xe & 0xfffffu) - RX_BIAS, ty0 = (int)(ye & 0xfffffu) - RX_BIAS;
-                        const uint32_t addr = 4u * (uint32_t)lane + slot_byte + 4u * (uint32_t)(SLOT_BIAS_DW + ((ty0 >> 5) - y0) * RS + ((tx0 >> 5) - x0));
-                        const bool lane_in = ((xe >> 27) & 1u) ? lane < TILE_W - nx : lane >= nx;
-                        const int jlo = ((ye >> 27) & 1u) ? 0 : ny, jhi = ((ye >> 27) & 1u) ? RX_TILE_H - ny : RX_TILE_H;
-                        if (lane_in) {
+                    // nothing of the plane in frame (x byte: n = 64, or every row out): no reads, no vector work
+                    if ((((xmasks >> (8 * k)) & 0x40u) | (((ymasks >> (8 * k)) & 0xffu) == 0xffu)) != 0u) continue;
+                    // (experiment 512 -- every plane sampled twice: the work of 8 planes per wavefront, DESIGN A.5b -- has served and is gone: its
+                    // run-time trip count no longer compiles with the immediates below)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+                    asm volatile("s_add_u32 m0, %[slot], %[fld]\n\t"
+                                 "s_and_b32 vcc_lo, %[fld], 0xc000\n\t"
+                                 "ds_read_addtid_b32 %[q0] offset:%[o0]\n\tds_read_addtid_b32 %[q1] offset:%[o1]\n\tds_read_addtid_b32 %[q2] offset:%[o2]\n\tds_read_addtid_b32 %[q3] offset:%[o3]\n\t"
+                                 "ds_read_addtid_b32 %[q4] offset:%[o4]\n\tds_read_addtid_b32 %[q5] offset:%[o5]\n\tds_read_addtid_b32 %[q6] offset:%[o6]\n\tds_read_addtid_b32 %[q7] offset:%[o7]\n\t"
+                                 "s_cselect_b64 exec, 0, -1\n\t"
+                                 "s_bfe_u32 vcc_lo, %[am], %[kb]\n\t"  // this plane's byte of the masks: SCC = not 0
+                                 "s_cbranch_scc1 1f\n\t"
+                                 "s_waitcnt lgkmcnt(0)\n\t"
+                                 "v_dot4_u32_u8 %[q0], %[q0], %[w], 0\n\tv_dot4_u32_u8 %[q1], %[q1], %[w], 0\n\tv_dot4_u32_u8 %[q2], %[q2], %[w], 0\n\tv_dot4_u32_u8 %[q3], %[q3], %[w], 0\n\t"
+                                 "v_dot4_u32_u8 %[q4], %[q4], %[w], 0\n\tv_dot4_u32_u8 %[q5], %[q5], %[w], 0\n\tv_dot4_u32_u8 %[q6], %[q6], %[w], 0\n\tv_dot4_u32_u8 %[q7], %[q7], %[w], 0\n\t"
+                                 "v_sad_u16 %[a0], %[q0], %[i0], %[a0]\n\tv_sad_u16 %[a1], %[q1], %[i1], %[a1]\n\tv_sad_u16 %[a2], %[q2], %[i2], %[a2]\n\tv_sad_u16 %[a3], %[q3], %[i3], %[a3]\n\t"
+                                 "v_sad_u16 %[a4], %[q4], %[i4], %[a4]\n\tv_sad_u16 %[a5], %[q5], %[i5], %[a5]\n\tv_sad_u16 %[a6], %[q6], %[i6], %[a6]\n\tv_sad_u16 %[a7], %[q7], %[i7], %[a7]\n\t"
+                                 "2:\n\t"
+                                 "s_mov_b64 exec, -1\n\t"
+                                 "s_branch 9f\n\t"
+                                 // ---- the tail: lanes in frame from the x byte
+                                 "1:\n\t"
+                                 "s_bfe_u32 vcc_lo, %[xm], %[nb]\n\t"        // n (6 bits)
+                                 "s_bitcmp1_b32 %[xm], %[sb]\n\t"            // side
+                                 "s_cbranch_scc1 3f\n\t"
+                                 "s_lshl_b64 exec, exec, vcc_lo\n\t"         // the first n lanes are out
+                                 "s_branch 4f\n\t"
+                                 "3:\n\t"
+                                 "s_lshr_b64 exec, exec, vcc_lo\n\t"         // the last n lanes are out
+                                 "4:\n\t"
+                                 "s_bitcmp1_b32 %[xm], %[eb]\n\t"            // n = 64: nothing in frame
+                                 "s_cselect_b64 exec, 0, exec\n\t"
+                                 "s_mov_b64 vcc, exec\n\t"
+                                 "s_waitcnt lgkmcnt(0)\n\t"
+                                 "v_dot4_u32_u8 %[q0], %[q0], %[w], 0\n\tv_dot4_u32_u8 %[q1], %[q1], %[w], 0\n\tv_dot4_u32_u8 %[q2], %[q2], %[w], 0\n\tv_dot4_u32_u8 %[q3], %[q3], %[w], 0\n\t"
+                                 "v_dot4_u32_u8 %[q4], %[q4], %[w], 0\n\tv_dot4_u32_u8 %[q5], %[q5], %[w], 0\n\tv_dot4_u32_u8 %[q6], %[q6], %[w], 0\n\tv_dot4_u32_u8 %[q7], %[q7], %[w], 0\n\t"
+                                 RX_ROW_TAIL(0) RX_ROW_TAIL(1) RX_ROW_TAIL(2) RX_ROW_TAIL(3) RX_ROW_TAIL(4) RX_ROW_TAIL(5) RX_ROW_TAIL(6) RX_ROW_TAIL(7)
+                                 "s_branch 2b\n\t"
+                                 "9:"
+                                 : [q0] "=&v"(qd[0][0]), [q1] "=&v"(qd[0][1]), [q2] "=&v"(qd[0][2]), [q3] "=&v"(qd[0][3]), [q4] "=&v"(qd[0][4]), [q5] "=&v"(qd[0][5]), [q6] "=&v"(qd[0][6]), [q7] "=&v"(qd[0][7]),
+                                   [a0] "+v"(acc[0][k]), [a1] "+v"(acc[1][k]), [a2] "+v"(acc[2][k]), [a3] "+v"(acc[3][k]), [a4] "+v"(acc[4][k]), [a5] "+v"(acc[5][k]), [a6] "+v"(acc[6][k]), [a7] "+v"(acc[7][k])
+                                 : [slot] "s"(slot_byte), [fld] "s"(fld[k]), [w] "s"(we[k]), [am] "s"(anymask), [xm] "s"(xmasks), [ym] "s"(ymasks),
+                                   [i0] "v"(Im255[0]), [i1] "v"(Im255[1]), [i2] "v"(Im255[2]), [i3] "v"(Im255[3]), [i4] "v"(Im255[4]), [i5] "v"(Im255[5]), [i6] "v"(Im255[6]), [i7] "v"(Im255[7]),
+                                   [o0] "n"(0), [o1] "n"(RS * 4), [o2] "n"(RS * 8), [o3] "n"(RS * 12), [o4] "n"(RS * 16), [o5] "n"(RS * 20), [o6] "n"(RS * 24), [o7] "n"(RS * 28),
+                                   [kb] "n"(8 * k | (8 << 16)), [nb] "n"(8 * k | (6 << 16)), [sb] "n"(8 * k + 7), [eb] "n"(8 * k + 6),
+                                   [yb0] "n"(8 * k + 0), [yb1] "n"(8 * k + 1), [yb2] "n"(8 * k + 2), [yb3] "n"(8 * k + 3), [yb4] "n"(8 * k + 4), [yb5] "n"(8 * k + 5), [yb6] "n"(8 * k + 6), [yb7] "n"(8 * k + 7)
+                                 : "m0", "scc", "vcc");
+#pragma clang diagnostic pop
+                }
+#undef RX_ROW_TAIL
+                // the planes whose certificate failed (a rounding boundary inside the tile), or whose offsets did not fit the record
+                if (special) {
+                    uintptr_t coldp = (uintptr_t)a.cold;
+                    asm volatile("" : "+s"(coldp));  // not loop-invariant for the optimiser: fetched here, not held in SGPRs over the loop
+                    const int dpad = RX_COLD(coldp, int, dpad);
+                    const cu32 xt = as_const<cu32>(RX_COLD(coldp, const uint32_t *, xt) + ((size_t)tx * a.V + v) * dpad + chunk * RX_PC + wave * RX_KW);
+                    const cu32 yt = as_const<cu32>(RX_COLD(coldp, const uint32_t *, yt) + ((size_t)ty * a.V + v) * dpad + chunk * RX_PC + wave * RX_KW);
+                    const uint32_t xsx = rdl(x0r, 6), yn = rdl(y0r, 3);
+                    const int x0 = (int)((xsx & 0xffffu) >> 2), y0 = (int)((yn >> 8) & 0x3fffu);
+                    const bool staged = (xsx >> 16) != 0u && (yn & 0xffu) != 0u;
 #pragma unroll
-                            for (int j = 0; j < 8; j++) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(qd[0][j]) : "v"(addr), "n"(j * RS * 4));
-                            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qd[0][0]), "+v"(qd[0][1]), "+v"(qd[0][2]), "+v"(qd[0][3]), "+v"(qd[0][4]), "+v"(qd[0][5]), "+v"(qd[0][6]), "+v"(qd[0][7]));
+                    for (int k = 0; k < RX_KW; k++) {
+                        if (!(fld[k] & 0xc000u)) continue;
+                        spacc += 1u << (8 * k);  // not FULL: this view's count does not go to every cell of the plane
+                        if (!staged) continue;
+                        const uint32_t xe = xt[k], ye = yt[k];
+                        const int nx = (int)((xe >> 20) & 127u), ny = (int)((ye >> 20) & 127u);
+                        if ((xe & ye) & RX_UNIFORM) {
+                            if (nx >= TILE_W || ny >= RX_TILE_H) continue;  // nothing in frame
+                            // a lane range (from the X entry) and a row range (from the Y entry) are in frame: the fast path under a mask,
+                            // the in-frame count per cell
+                            const int tx0 = (int)(xe & 0xfffffu) - RX_BIAS, ty0 = (int)(ye & 0xfffffu) - RX_BIAS;
+                            const uint32_t addr = 4u * (uint32_t)lane + slot_byte + 4u * (uint32_t)(SLOT_BIAS_DW + ((ty0 >> 5) - y0) * RS + ((tx0 >> 5) - x0));
+                            const bool lane_in = ((xe >> 27) & 1u) ? lane < TILE_W - nx : lane >= nx;
+                            const int jlo = ((ye >> 27) & 1u) ? 0 : ny, jhi = ((ye >> 27) & 1u) ? RX_TILE_H - ny : RX_TILE_H;
+                            if (lane_in) {
 #pragma unroll
-                            for (int j = 0; j < 8; j++)
-                                if (j >= jlo && j < jhi) acc[j][k] = sad_u16(__builtin_amdgcn_udot4(qd[0][j], we[k], 0u, false), Im255[j], acc[j][k] + (1u << 24));
+                                for (int j = 0; j < 8; j++) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(qd[0][j]) : "v"(addr), "n"(j * RS * 4));
+                                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qd[0][0]), "+v"(qd[0][1]), "+v"(qd[0][2]), "+v"(qd[0][3]), "+v"(qd[0][4]), "+v"(qd[0][5]), "+v"(qd[0][6]), "+v"(qd[0][7]));
+#pragma unroll
+                                for (int j = 0; j < 8; j++)
+                                    if (j >= jlo && j < jhi) acc[j][k] = sad_u16(__builtin_amdgcn_udot4(qd[0][j], we[k], 0u, false), Im255[j], acc[j][k] + (1u << 24));
+                            }
+                            continue;
                         }
-                        continue;
-                    }
-                    // A certificate failed (a rounding boundary inside the tile: ~0.3 % of the planes on the SURVEY 8d ring): the contract's
-                    // expression per lane (columns) and per row, then one pass per group of lanes that share a phase and a texel offset
-                    // (usually two groups), each with wave-uniform weights and LDS bases like the fast path.
-                    const cf32 q = as_const<cf32>(RX_COLD(coldp, const float *, Q) + 12 * v);
-                    const float z = as_const<cf32>(RX_COLD(coldp, const float *, z))[min(chunk * RX_PC + wave * RX_KW + k, a.D - 1)];
-                    const float invW = RX_COLD(coldp, float, invW), invH = RX_COLD(coldp, float, invH);
-                    const cu32 lut = as_const<cu32>(RX_COLD(coldp, const uint32_t *, lut));
-                    const uint32_t lo_bits = __builtin_bit_cast(uint32_t, RX_MAGIC + 132.0f);
-                    const uint32_t hix_bits = lo_bits + 256u * (uint32_t)a.W, hiy_bits = lo_bits + 256u * (uint32_t)a.H;  // floats in [2^23, 2^24): ulp 1
-                    const float r256 = rect_r256(q);
-                    const uint32_t txb = __builtin_bit_cast(uint32_t, rect_tx(q, r256, z, col, invW));
-                    const bool inx = col_ok && txb > lo_bits && txb < hix_bits;
-                    const int tx3 = (int)((txb & 0x3fffffu) >> 3) - 32 * lane;
-                    const uint32_t tyv = __builtin_bit_cast(uint32_t, rect_ty(q, r256, z, row0 + (lane & 7), invH));
-                    unsigned long long remaining = __builtin_amdgcn_ballot_w64(inx);
-                    while (remaining) {
-                        const int t = __builtin_amdgcn_readlane(tx3, (int)__builtin_ctzll(remaining));
-                        const bool mine = inx && tx3 == t;
-                        remaining &= ~__builtin_amdgcn_ballot_w64(mine);
-                        const uint32_t kx = (uint32_t)t & 31u;
-                        const int ixrel = (t >> 5) - x0;
+                        // A certificate failed (a rounding boundary inside the tile: ~0.3 % of the planes on the SURVEY 8d ring): the contract's
+                        // expression per lane (columns) and per row, then one pass per group of lanes that share a phase and a texel offset
+                        // (usually two groups), each with wave-uniform weights and LDS bases like the fast path.
+                        const cf32 q = as_const<cf32>(RX_COLD(coldp, const float *, Q) + 12 * v);
+                        const float z = as_const<cf32>(RX_COLD(coldp, const float *, z))[min(chunk * RX_PC + wave * RX_KW + k, a.D - 1)];
+                        const float invW = RX_COLD(coldp, float, invW), invH = RX_COLD(coldp, float, invH);
+                        const cu32 lut = as_const<cu32>(RX_COLD(coldp, const uint32_t *, lut));
+                        const uint32_t lo_bits = __builtin_bit_cast(uint32_t, RX_MAGIC + 132.0f);
+                        const uint32_t hix_bits = lo_bits + 256u * (uint32_t)a.W, hiy_bits = lo_bits + 256u * (uint32_t)a.H;  // floats in [2^23, 2^24): ulp 1
+                        const float r256 = rect_r256(q);
+                        const uint32_t txb = __builtin_bit_cast(uint32_t, rect_tx(q, r256, z, col, invW));
+                        const bool inx = col_ok && txb > lo_bits && txb < hix_bits;
+                        const int tx3 = (int)((txb & 0x3fffffu) >> 3) - 32 * lane;
+                        const uint32_t tyv = __builtin_bit_cast(uint32_t, rect_ty(q, r256, z, row0 + (lane & 7), invH));
+                        unsigned long long remaining = __builtin_amdgcn_ballot_w64(inx);
+                        while (remaining) {
+                            const int t = __builtin_amdgcn_readlane(tx3, (int)__builtin_ctzll(remaining));
+                            const bool mine = inx && tx3 == t;
+                            remaining &= ~__builtin_amdgcn_ballot_w64(mine);
+                            const uint32_t kx = (uint32_t)t & 31u;
+                            const int ixrel = (t >> 5) - x0;
 #pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            const uint32_t tyb = (uint32_t)__builtin_amdgcn_readlane((int)tyv, j);
-                            if (tyb > lo_bits && tyb < hiy_bits && row0 + j < a.H) {
-                                const uint32_t uy = tyb & 0x3fffffu;
-                                const uint32_t w = lut[((uy >> 3) & 31u) * 32u + kx];
-                                const uint32_t addr = 4u * (uint32_t)lane + slot_byte + 4u * (uint32_t)(SLOT_BIAS_DW + ((int)(uy >> 8) - y0) * RS + ixrel);
-                                if (mine) {
-                                    uint32_t quad;
-                                    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(quad) : "v"(addr));
-                                    acc[j][k] = sad_u16(__builtin_amdgcn_udot4(quad, w, 0u, false), Im255[j], acc[j][k] + (1u << 24));
+                            for (int j = 0; j < 8; j++) {
+                                const uint32_t tyb = (uint32_t)__builtin_amdgcn_readlane((int)tyv, j);
+                                if (tyb > lo_bits && tyb < hiy_bits && row0 + j < a.H) {
+                                    const uint32_t uy = tyb & 0x3fffffu;
+                                    const uint32_t w = lut[((uy >> 3) & 31u) * 32u + kx];
+                                    const uint32_t addr = 4u * (uint32_t)lane + slot_byte + 4u * (uint32_t)(SLOT_BIAS_DW + ((int)(uy >> 8) - y0) * RS + ixrel);
+                                    if (mine) {
+                                        uint32_t quad;
+                                        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(quad) : "v"(addr));
+                                        acc[j][k] = sad_u16(__builtin_amdgcn_udot4(quad, w, 0u, false), Im255[j], acc[j][k] + (1u << 24));
+                                    }
                                 }
                             }
                         }
@@ -880,6 +936,61 @@ int sweep_rect_plan(mvs_ctx *ctx, PlanHook *between)
     ctx->rect_dpad = rt.dpad;
     plan_rect_pack<<<(unsigned)((4 * nb + 255) / 256), 256, 0, ctx->stream>>>(q, rt, rs);
     MVS_HIP(ctx, hipGetLastError());
+    if (ctx->hooks.rect_verbose) {
+        // which region bodies the sweep kernel will run.  CLEAN regions (tile, chunk, view, wavefront): no flag in the four fields and
+        // no mask byte, in the X record of the tile column and in the Y record of the tile row.  Per (region, plane) of the others:
+        // nothing in frame (x byte n = 64 or y byte 0xff in either record: the plane is branched over), a failed certificate (a flag
+        // in either record: the cold block), and the border planes by the side that is out of frame (left / right / top / bottom).
+        const RectSizes z = rect_sizes(q);
+        std::vector<uint32_t> xw(z.nxw), yr(z.nyr);
+        MVS_HIP(ctx, hipMemcpyAsync(xw.data(), rt.xw, z.nxw * 4, hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(ctx, hipMemcpyAsync(yr.data(), rt.yr, z.nyr * 4, hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const size_t per = (size_t)q.V * q.nchunks * 4;  // records per tile column / tile row
+        const double TX = q.tiles_x, TY = q.tiles_y;
+        double clean = 0.0, none = 0.0, flagged = 0.0, side[4] = {0.0, 0.0, 0.0, 0.0};
+        for (size_t e = 0; e < per; e++) {
+            size_t cx = 0, cy = 0;
+            for (int t = 0; t < q.tiles_x; t++) {
+                const uint32_t *r = xw.data() + ((size_t)t * per + e) * 8;
+                cx += ((r[0] | r[1]) & 0x40004000u) == 0u && r[7] == 0u;
+            }
+            for (int t = 0; t < q.tiles_y; t++) {
+                const uint32_t *r = yr.data() + ((size_t)t * per + e) * 8;
+                cy += ((r[0] | r[1]) & 0x80008000u) == 0u && r[4] == 0u;
+            }
+            clean += (double)cx * (double)cy;
+            for (int k = 0; k < RX_KW; k++) {
+                double xn = 0, xf = 0, yn = 0, yf = 0, l = 0, rt_ = 0, tp = 0, bt = 0;
+                for (int t = 0; t < q.tiles_x; t++) {
+                    const uint32_t *r = xw.data() + ((size_t)t * per + e) * 8;
+                    const uint32_t f = (r[k >> 1] >> (16 * (k & 1))) & 0xffffu, m = (r[7] >> (8 * k)) & 0xffu;
+                    xf += (f & 0x4000u) != 0u;
+                    xn += (m & 0x40u) != 0u;
+                    l += m != 0u && !(m & 0x40u) && !(m & 0x80u);
+                    rt_ += m != 0u && !(m & 0x40u) && (m & 0x80u);
+                }
+                for (int t = 0; t < q.tiles_y; t++) {
+                    const uint32_t *r = yr.data() + ((size_t)t * per + e) * 8;
+                    const uint32_t f = (r[k >> 1] >> (16 * (k & 1))) & 0xffffu, m = (r[4] >> (8 * k)) & 0xffu;
+                    yf += (f & 0x8000u) != 0u;
+                    yn += m == 0xffu;
+                    tp += m != 0u && m != 0xffu && (m & 1u);
+                    bt += m != 0u && m != 0xffu && (m & 0x80u);
+                }
+                none += TX * TY - (TX - xn) * (TY - yn);
+                flagged += TX * TY - (TX - xf) * (TY - yf);
+                side[0] += l * TY;
+                side[1] += rt_ * TY;
+                side[2] += tp * TX;
+                side[3] += bt * TX;
+            }
+        }
+        const double nreg = (double)per * TX * TY, npl = nreg * RX_KW;
+        fprintf(stderr, "sweep_rect_plan: clean regions %.2f %% of %.0f; planes: nothing in frame %.3f %%, failed certificate %.3f %%, "
+                "border left %.3f %% right %.3f %% top %.3f %% bottom %.3f %%\n", 100.0 * clean / nreg, nreg, 100.0 * none / npl,
+                100.0 * flagged / npl, 100.0 * side[0] / npl, 100.0 * side[1] / npl, 100.0 * side[2] / npl, 100.0 * side[3] / npl);
+    }
     // the cold block (device memory, after the tables)
     RectCold cold;
     cold.main_img = main_image_ptr(ctx);
