@@ -7,15 +7,16 @@
 // OpenCV's organisation; the operation order is the one documented in oracle/flow_oracle.c, which these kernels
 // reproduce bit for bit (f32 ops one rounding each under -ffp-contract=off, f64 where OpenCV accumulates in double).
 //
-// Farneback, per pyramid level (coarse to fine): gauss (rows, columns) -> resize_linear -> polyexp_vert/polyexp_horiz,
-// both frames per launch (blockIdx.z), then update_matrices and `iterations` x farneback_iteration_fused (vertical box
-// sums in LDS + horizontal sums + 2x2 solve + the next update matrices; the three separate kernels remain as the A/B form).
+// Farneback: the pyramid preparation -- gauss (rows and columns in one launch) -> resize_linear -> polynomial expansion, every
+// frame per launch (blockIdx.z); all levels in three launches up to FB_BATCH_PREP_MAX_PIXELS, level by level above -- then per
+// level (coarse to fine) the flow carried down + the first update matrices, and `iterations` x one fused iteration (vertical box
+// sums in LDS + horizontal sums + 2x2 solve + the next update matrices; the three-launch form only for windows beyond FB_MAXM).
 // Everything stays in one HBM arena per context; the reference's per-level Mat allocations and the CPU
 // round trip of every intermediate disappear.
 //
 // Variational refinement: warp_q5 -> avg_diff -> central differences -> 5 x var_fixed_point_fused (data term,
 // diffusivity, smoothness gather and the 5 red-black SOR sweeps of one fixed-point iteration in ONE launch by temporal
-// blocking in LDS; the 13 separate kernels remain as the A/B form) -> add increment.
+// blocking in LDS) -> add increment.
 #include "mvs_internal.hpp"
 
 #include <atomic>
@@ -45,12 +46,6 @@ struct Taps {
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);    \
     if (x >= w || y >= h) return;
 
-__global__ __launch_bounds__(256) void zero_f32_kernel(float *__restrict__ d, size_t n)  // (test hook MVS_FLOW_GRAPH=2: a kernel in place of the captured hipMemsetAsync nodes)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) d[i] = 0.0f;
-}
-
 __global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t *__restrict__ s, float *__restrict__ d, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -66,35 +61,11 @@ __global__ __launch_bounds__(256) void u8_to_f32_pair_kernel(const uint8_t *__re
     }
 }
 
-// symmetric separable filter, REFLECT_101: acc = k[c]*S[0]; acc += k[c+j]*(S[+j] + S[-j])
-template <bool COLS>
-__global__ __launch_bounds__(256) void gauss_kernel(const float *__restrict__ src, int w, int h, Taps t, int ksize,
-                                                    float *__restrict__ dst, ptrdiff_t src_z = 0, ptrdiff_t dst_z = 0)
-{
-    PIX2D
-    src += (ptrdiff_t)blockIdx.z * src_z;  // blockIdx.z: the second frame of a pair, processed by the same launch
-    dst += (ptrdiff_t)blockIdx.z * dst_z;
-    const int c = ksize / 2;
-    float acc = t.k[c] * src[(size_t)y * w + x];
-    for (int j = 1; j <= c; j++) {
-        float a, b;
-        if (COLS) {
-            a = src[(size_t)refl101(y + j, h) * w + x];
-            b = src[(size_t)refl101(y - j, h) * w + x];
-        } else {
-            a = src[(size_t)y * w + refl101(x + j, w)];
-            b = src[(size_t)y * w + refl101(x - j, w)];
-        }
-        acc += t.k[c + j] * (a + b);
-    }
-    dst[(size_t)y * w + x] = acc;
-}
-
-// Both passes of the separable filter in ONE launch (round 5): a workgroup stages its 64 x 16 output tile's (64 + 2c) x (16 + 2c) input
-// neighbourhood in LDS (reflected coordinates resolved while staging), runs the row filter over the 16 + 2c rows into a second LDS array and
-// the column filter from there -- the expressions of gauss_kernel<false> and <true> on the same values in the same order (bit-identical),
-// without the intermediate image's round trip through HBM: cv::GaussianBlur of BOTH full-resolution frames is paid once per pyramid
-// level (fastPyramids false), 22 passes over 16.6 MB per 1080p flow.
+// The symmetric separable filter, REFLECT_101 (acc = k[c]*S[0]; acc += k[c+j]*(S[+j] + S[-j])), both passes in ONE launch (round 5): a
+// workgroup stages its 64 x 16 output tile's (64 + 2c) x (16 + 2c) input neighbourhood in LDS (reflected coordinates resolved while staging),
+// runs the row filter over the 16 + 2c rows into a second LDS array and the column filter from there -- the oracle's two passes on the same
+// values in the same order (bit-identical), without the intermediate image's round trip through HBM: cv::GaussianBlur of BOTH
+// full-resolution frames is paid once per pyramid level (fastPyramids false), 22 passes over 16.6 MB per 1080p flow.
 // (body: src / dst already point at the image; kc[j] = tap c + j of the symmetric kernel, j = 0 .. c)
 __device__ __forceinline__ void gauss_fused_body(const float *__restrict__ src, int w, int h, const float *__restrict__ kc, int c, float *__restrict__ dst,
                                                  int X0, int Y0, float *__restrict__ g_lds)
@@ -106,7 +77,7 @@ __device__ __forceinline__ void gauss_fused_body(const float *__restrict__ src, 
         in[i] = src[(size_t)refl101(Y0 - c + r, h) * w + refl101(X0 - c + q, w)];
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 64 * IH; i += 256) {  // rows: gauss_kernel<false> at (refl(Y0 - c + r), X0 + x)
+    for (int i = threadIdx.x; i < 64 * IH; i += 256) {  // the row pass at (refl(Y0 - c + r), X0 + x)
         const int r = i >> 6, x = i & 63;
         const float *p = in + r * IW + x + c;
         float acc = kc[0] * p[0];
@@ -114,7 +85,7 @@ __device__ __forceinline__ void gauss_fused_body(const float *__restrict__ src, 
         tmp[i] = acc;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 64 * 16; i += 256) {  // columns: gauss_kernel<true> at (Y0 + r, X0 + x)
+    for (int i = threadIdx.x; i < 64 * 16; i += 256) {  // the column pass at (Y0 + r, X0 + x)
         const int r = i >> 6, x = i & 63, gy = Y0 + r, gx = X0 + x;
         if (gx >= w || gy >= h) continue;
         const float *p = tmp + (r + c) * 64 + x;
@@ -225,62 +196,11 @@ struct PolyTaps {
     int n;
 };
 
-// FarnebackPolyExp, vertical pass: row[x] = (sum g I, sum y g I, sum y^2 g I) over the column, replicate border
-__global__ __launch_bounds__(256) void polyexp_vert(const float *__restrict__ src, int w, int h, PolyTaps t,
-                                                    float *__restrict__ row3, ptrdiff_t src_z = 0, ptrdiff_t dst_z = 0)
-{
-    PIX2D
-    src += (ptrdiff_t)blockIdx.z * src_z;
-    row3 += (ptrdiff_t)blockIdx.z * dst_z;
-    float t0 = src[(size_t)y * w + x] * t.g[0], t1 = 0.f, t2 = 0.f;
-    for (int k = 1; k <= t.n; k++) {
-        const float a = src[(size_t)(y - k > 0 ? y - k : 0) * w + x];
-        const float b = src[(size_t)(y + k < h - 1 ? y + k : h - 1) * w + x];
-        const float p = a + b;
-        t0 = t0 + t.g[k] * p;
-        t1 = t1 + t.xg[k] * (b - a);
-        t2 = t2 + t.xxg[k] * p;
-    }
-    float *r = row3 + ((size_t)y * w + x) * 3;
-    r[0] = t0;
-    r[1] = t1;
-    r[2] = t2;
-}
-
-// horizontal pass + projection onto the polynomial basis: 5 coefficients per pixel (y, x, y^2, x^2, xy)
-__global__ __launch_bounds__(256) void polyexp_horiz(const float *__restrict__ row3, int w, int h, PolyTaps t,
-                                                     float *__restrict__ dst5, ptrdiff_t src_z = 0, ptrdiff_t dst_z = 0)
-{
-    PIX2D
-    row3 += (ptrdiff_t)blockIdx.z * src_z;
-    dst5 += (ptrdiff_t)blockIdx.z * dst_z;
-    const float *base = row3 + (size_t)y * w * 3;
-    const float *c = base + (size_t)x * 3;
-    float g0 = t.g[0];
-    double b1 = c[0] * g0, b2 = 0, b3 = c[1] * g0, b4 = 0, b5 = c[2] * g0, b6 = 0;
-    for (int k = 1; k <= t.n; k++) {
-        const float *p = base + (size_t)clampi(x + k, 0, w - 1) * 3;
-        const float *m = base + (size_t)clampi(x - k, 0, w - 1) * 3;
-        const double tg = p[0] + m[0];
-        g0 = t.g[k];
-        b1 += tg * g0;
-        b4 += tg * t.xxg[k];
-        b2 += (p[0] - m[0]) * t.xg[k];
-        b3 += (p[1] + m[1]) * g0;
-        b6 += (p[1] - m[1]) * t.xg[k];
-        b5 += (p[2] + m[2]) * g0;
-    }
-    float *d = dst5 + ((size_t)y * w + x) * 5;
-    d[1] = (float)(b2 * t.ig11);
-    d[0] = (float)(b3 * t.ig11);
-    d[3] = (float)(b1 * t.ig03 + b4 * t.ig33);
-    d[2] = (float)(b1 * t.ig03 + b5 * t.ig33);
-    d[4] = (float)(b6 * t.ig55);
-}
-
-// polyexp_vert + polyexp_horiz in one launch (round 5): the tile's (16 + 2n) x (64 + 2n) neighbourhood staged in LDS with the replicate
-// border resolved while staging, the vertical sums of its 16 rows x (64 + 2n) columns into a second LDS array, the horizontal pass from
-// there -- the same expressions on the same values (bit-identical), no round trip of the 12-byte-per-pixel intermediate through HBM.
+// FarnebackPolyExp in one launch (round 5): the vertical pass (row[x] = (sum g I, sum y g I, sum y^2 g I) over the column, replicate
+// border) and the horizontal pass + projection onto the polynomial basis (5 coefficients per pixel: y, x, y^2, x^2, xy).  The tile's
+// (16 + 2n) x (64 + 2n) neighbourhood is staged in LDS with the replicate border resolved while staging, the vertical sums of its 16 rows x
+// (64 + 2n) columns go into a second LDS array, the horizontal pass runs from there -- the oracle's expressions on the same values
+// (bit-identical), no round trip of the 12-byte-per-pixel intermediate through HBM.
 __device__ __forceinline__ void polyexp_fused_body(const float *__restrict__ src, int w, int h, const PolyTaps &t, float *__restrict__ dst5, int X0, int Y0,
                                                    float *__restrict__ p_lds)
 {
@@ -292,7 +212,7 @@ __device__ __forceinline__ void polyexp_fused_body(const float *__restrict__ src
         in[i] = src[(size_t)clampi(Y0 - n + r, 0, h - 1) * w + clampi(X0 - n + q, 0, w - 1)];
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 16 * IW; i += 256) {  // polyexp_vert at (Y0 + r, clamp(X0 - n + q)): rows y -+ k are tile rows r + n -+ k
+    for (int i = threadIdx.x; i < 16 * IW; i += 256) {  // vertical pass at (Y0 + r, clamp(X0 - n + q)): rows y -+ k are tile rows r + n -+ k
         const int r = i / IW, q = i - r * IW;
         const float *c = in + (r + n) * IW + q;
         float t0 = c[0] * t.g[0], t1 = 0.f, t2 = 0.f;
@@ -309,7 +229,7 @@ __device__ __forceinline__ void polyexp_fused_body(const float *__restrict__ src
         o[2] = t2;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 16 * 64; i += 256) {  // polyexp_horiz at (Y0 + r, X0 + x): columns x +- k are tile columns x + n +- k
+    for (int i = threadIdx.x; i < 16 * 64; i += 256) {  // horizontal pass at (Y0 + r, X0 + x): columns x +- k are tile columns x + n +- k
         const int r = i >> 6, x = i & 63, gy = Y0 + r, gx = X0 + x;
         if (gx >= w || gy >= h) continue;
         const float *c = row3 + ((size_t)r * IW + x + n) * 3;
@@ -584,8 +504,8 @@ __global__ __launch_bounds__(256) void farneback_iteration_fused(const float *__
 // (2m + PX) / PX LDS reads per horizontal sum instead of 2m + 1 (the kernel above was bound by exactly those: 910 bytes of loads per
 // pixel and iteration at 1080p).  A workgroup owns 64 x TY pixels, TY = 2 PY = 4 PX; the vertical sums of its 64 + 2m columns live in LDS
 // as vs[row][channel][column], the column index padded by one slot every PX columns so that the lanes of a wavefront -- PX columns apart
-// -- hit different banks (stride PX + 1 doubles, odd).  Needs 2m >= PY - 1 (head and tail of the walk are unrolled); smaller windows,
-// and the test hook MVS_FB_DIRECT_BOX, take the kernel above.
+// -- hit different banks (stride PX + 1 doubles, odd).  Needs 2m >= PY - 1 (head and tail of the walk are unrolled); smaller windows
+// (m < 4) take the kernel above.
 template <int N>
 struct FbAcc {
     double s[N][5];
@@ -793,164 +713,39 @@ __global__ __launch_bounds__(256) void warp_q5_kernel(const float *__restrict__ 
     Iz[p] = warped - I0[p];
 }
 
-template <bool DY>
-__global__ __launch_bounds__(256) void diff_kernel(const float *__restrict__ a, int w, int h, float *__restrict__ o)
-{
-    PIX2D
-    if (DY)
-        o[(size_t)y * w + x] = a[(size_t)clampi(y + 1, 0, h - 1) * w + x] - a[(size_t)clampi(y - 1, 0, h - 1) * w + x];
-    else
-        o[(size_t)y * w + x] = a[(size_t)y * w + clampi(x + 1, 0, w - 1)] - a[(size_t)y * w + clampi(x - 1, 0, w - 1)];
-}
-
 struct VarBufs {
     float *Wu, *Wv, *du, *dv, *Iz, *Ix, *Iy, *Ixx, *Ixy, *Iyy, *Ixz, *Iyz, *a11, *a12, *a22, *b1, *b2, *wgt;
 };
 
-// All seven derivative images of the refinement in ONE launch (round 6; seven diff_kernel launches before -- a 640 x 480 refinement is launches, not
+// All seven derivative images of the refinement in ONE launch (round 6; seven launches before -- a 640 x 480 refinement is launches, not
 // bytes, and mvs_process_frame runs four of them per main frame): Ix, Iy of A; Ixz, Iyz of Iz; Ixx, Ixy of Ix; Iyy of Iy.  A second derivative needs the
 // first one at the pixel's neighbours; each of those is ONE subtraction of two values of A, so it is formed again here from A -- the same operation on the
-// same operands as diff_kernel's stored value: the same bits -- instead of waiting for a kernel that stores it.
+// same operands as the oracle's stored first derivative: the same bits -- instead of waiting for a kernel that stores it.
 __global__ __launch_bounds__(256) void var_derivatives_kernel(const float *__restrict__ A, const float *__restrict__ Iz, int w, int h, VarBufs B)
 {
     PIX2D
     auto cx = [&](int v) { return clampi(v, 0, w - 1); };
     auto cy = [&](int v) { return clampi(v, 0, h - 1); };
-    auto ddx = [&](const float *__restrict__ a, int yy, int xx) { return a[(size_t)yy * w + cx(xx + 1)] - a[(size_t)yy * w + cx(xx - 1)]; };   // diff_kernel<false> at (yy, xx)
-    auto ddy = [&](const float *__restrict__ a, int yy, int xx) { return a[(size_t)cy(yy + 1) * w + xx] - a[(size_t)cy(yy - 1) * w + xx]; };   // diff_kernel<true> at (yy, xx)
+    auto ddx = [&](const float *__restrict__ a, int yy, int xx) { return a[(size_t)yy * w + cx(xx + 1)] - a[(size_t)yy * w + cx(xx - 1)]; };   // the oracle's ddx at (yy, xx)
+    auto ddy = [&](const float *__restrict__ a, int yy, int xx) { return a[(size_t)cy(yy + 1) * w + xx] - a[(size_t)cy(yy - 1) * w + xx]; };   // the oracle's ddy at (yy, xx)
     const size_t p = (size_t)y * w + x;
     B.Ix[p] = ddx(A, y, x);
     B.Iy[p] = ddy(A, y, x);
     B.Ixz[p] = ddx(Iz, y, x);
     B.Iyz[p] = ddy(Iz, y, x);
-    B.Ixx[p] = ddx(A, y, cx(x + 1)) - ddx(A, y, cx(x - 1));   // diff_kernel<false>(Ix)
-    B.Ixy[p] = ddx(A, cy(y + 1), x) - ddx(A, cy(y - 1), x);   // diff_kernel<true>(Ix)
-    B.Iyy[p] = ddy(A, cy(y + 1), x) - ddy(A, cy(y - 1), x);   // diff_kernel<true>(Iy)
-}
-
-__global__ __launch_bounds__(256) void var_data_term(VarBufs B, int w, int h)
-{
-    PIX2D
-    const size_t p = (size_t)y * w + x;
-    const float zeta2 = 0.1f * 0.1f, eps2 = 0.001f * 0.001f, gamma2 = 10.f / 2, delta2 = 5.f / 2;
-    const float Ix = B.Ix[p], Iy = B.Iy[p], Iz = B.Iz[p], Ixx = B.Ixx[p], Ixy = B.Ixy[p], Iyy = B.Iyy[p], Ixz = B.Ixz[p],
-                Iyz = B.Iyz[p], du = B.du[p], dv = B.dv[p];
-    float derivNorm = Ix * Ix + Iy * Iy + zeta2;
-    const float Ik1z = Iz + Ix * du + Iy * dv;
-    float weight = (delta2 / sqrtf(Ik1z * Ik1z / derivNorm + eps2)) / derivNorm;
-    float A11 = weight * (Ix * Ix) + zeta2;
-    float A12 = weight * (Ix * Iy);
-    float A22 = weight * (Iy * Iy) + zeta2;
-    float B1 = -weight * (Iz * Ix);
-    float B2 = -weight * (Iz * Iy);
-    derivNorm = Ixx * Ixx + Ixy * Ixy + zeta2;
-    const float derivNorm2 = Iyy * Iyy + Ixy * Ixy + zeta2;
-    const float Ik1zx = Ixz + Ixx * du + Ixy * dv;
-    const float Ik1zy = Iyz + Ixy * du + Iyy * dv;
-    weight = gamma2 / sqrtf(Ik1zx * Ik1zx / derivNorm + Ik1zy * Ik1zy / derivNorm2 + eps2);
-    A11 += weight * (Ixx * Ixx / derivNorm + Ixy * Ixy / derivNorm2);
-    A12 += weight * (Ixx * Ixy / derivNorm + Ixy * Iyy / derivNorm2);
-    A22 += weight * (Ixy * Ixy / derivNorm + Iyy * Iyy / derivNorm2);
-    B1 += -weight * (Ixx * Ixz / derivNorm + Ixy * Iyz / derivNorm2);
-    B2 += -weight * (Ixy * Ixz / derivNorm + Iyy * Iyz / derivNorm2);
-    B.a11[p] = A11;
-    B.a12[p] = A12;
-    B.a22[p] = A22;
-    B.b1[p] = B1;
-    B.b2[p] = B2;
-}
-
-__global__ __launch_bounds__(256) void var_diffusivity(VarBufs B, int w, int h)
-{
-    PIX2D
-    const size_t p = (size_t)y * w + x;
-    const float eps2 = 0.001f * 0.001f, alpha2 = 20.f / 2;
-    const float cu = B.Wu[p] + B.du[p], cv = B.Wv[p] + B.dv[p];
-    const float ux = x + 1 < w ? (B.Wu[p + 1] + B.du[p + 1]) - cu : 0.f, vx = x + 1 < w ? (B.Wv[p + 1] + B.dv[p + 1]) - cv : 0.f;
-    const float uy = y + 1 < h ? (B.Wu[p + w] + B.du[p + w]) - cu : 0.f, vy = y + 1 < h ? (B.Wv[p + w] + B.dv[p + w]) - cv : 0.f;
-    B.wgt[p] = alpha2 / sqrtf(ux * ux + vx * vx + uy * uy + vy * vy + eps2);
-}
-
-__global__ __launch_bounds__(256) void var_smooth_gather(VarBufs B, int w, int h)
-{
-    PIX2D
-    const size_t p = (size_t)y * w + x;
-    float A11 = B.a11[p], A22 = B.a22[p], B1 = B.b1[p], B2 = B.b2[p];
-    if (x > 0) {
-        const float wt = B.wgt[p - 1];
-        B1 -= wt * (B.Wu[p] - B.Wu[p - 1]);
-        B2 -= wt * (B.Wv[p] - B.Wv[p - 1]);
-        A11 += wt;
-        A22 += wt;
-    }
-    if (x + 1 < w) {
-        const float wt = B.wgt[p];
-        B1 += wt * (B.Wu[p + 1] - B.Wu[p]);
-        B2 += wt * (B.Wv[p + 1] - B.Wv[p]);
-        A11 += wt;
-        A22 += wt;
-    }
-    if (y > 0) {
-        const float wt = B.wgt[p - w];
-        B1 -= wt * (B.Wu[p] - B.Wu[p - w]);
-        B2 -= wt * (B.Wv[p] - B.Wv[p - w]);
-        A11 += wt;
-        A22 += wt;
-    }
-    if (y + 1 < h) {
-        const float wt = B.wgt[p];
-        B1 += wt * (B.Wu[p + w] - B.Wu[p]);
-        B2 += wt * (B.Wv[p + w] - B.Wv[p]);
-        A11 += wt;
-        A22 += wt;
-    }
-    B.a11[p] = A11;
-    B.a22[p] = A22;
-    B.b1[p] = B1;
-    B.b2[p] = B2;
-}
-
-// one colour of a red-black SOR sweep: thread per pixel of that colour
-__global__ __launch_bounds__(256) void var_sor_pass(VarBufs B, int w, int h, int colour)
-{
-    const int xi = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int x = 2 * xi + ((y + colour) & 1);
-    if (x >= w || y >= h) return;
-    const size_t p = (size_t)y * w + x;
-    const float omega = 1.6f;
-    float sU = 0.f, sV = 0.f;
-    if (x > 0) {
-        sU += B.wgt[p - 1] * B.du[p - 1];
-        sV += B.wgt[p - 1] * B.dv[p - 1];
-    }
-    if (x + 1 < w) {
-        sU += B.wgt[p] * B.du[p + 1];
-        sV += B.wgt[p] * B.dv[p + 1];
-    }
-    if (y > 0) {
-        sU += B.wgt[p - w] * B.du[p - w];
-        sV += B.wgt[p - w] * B.dv[p - w];
-    }
-    if (y + 1 < h) {
-        sU += B.wgt[p] * B.du[p + w];
-        sV += B.wgt[p] * B.dv[p + w];
-    }
-    float du = B.du[p], dv = B.dv[p];
-    du += omega * ((sU + B.b1[p] - dv * B.a12[p]) / B.a11[p] - du);
-    dv += omega * ((sV + B.b2[p] - du * B.a12[p]) / B.a22[p] - dv);
-    B.du[p] = du;
-    B.dv[p] = dv;
+    B.Ixx[p] = ddx(A, y, cx(x + 1)) - ddx(A, y, cx(x - 1));   // ddx(Ix)
+    B.Ixy[p] = ddx(A, cy(y + 1), x) - ddx(A, cy(y - 1), x);   // ddy(Ix)
+    B.Iyy[p] = ddy(A, cy(y + 1), x) - ddy(A, cy(y - 1), x);   // ddy(Iy)
 }
 
 // One fixed-point iteration of the refinement in ONE launch: data term, diffusivity, smoothness gather and the 5
-// red-black SOR sweeps (10 half-steps), which the kernels above run as 13 launches of a few microseconds each.
-// A 1024-thread workgroup owns a VT_W x VT_H core and works on the core plus a VT_HALO-cell halo held in LDS
+// red-black SOR sweeps (10 half-steps), which the statement in oracle/flow_oracle.c (orc_variational_refine) runs as
+// 13 passes over the image.  A 1024-thread workgroup owns a VT_W x VT_H core and works on the core plus a VT_HALO-cell halo held in LDS
 // (temporal blocking): a half-step only reads the four neighbours, so after half-step s every cell at least s+1 cells
 // inside the region edge holds exactly the value the global sweep would have produced -- with a halo of 10 the core
 // is exact after all 10 half-steps (image borders do not shrink the valid set: there is no neighbour to be wrong).
-// Every cell is evaluated with the expressions of the kernels above in the same order, so the result is bit-identical
-// (tests/test_flow_gpu.py compares both forms).  du/dv ping-pong between two buffers because neighbouring workgroups
+// Every cell is evaluated with the oracle's expressions in the same order, so the result is bit-identical
+// (tests/test_flow_gpu.py compares mvs_flow with the oracle).  du/dv ping-pong between two buffers because neighbouring workgroups
 // read each other's halo at the start.
 //
 // Thread mapping (round 6, second form): a thread owns SLOTS, a slot = two horizontally adjacent cells (2j, 2j + 1) of a region
@@ -1295,7 +1090,7 @@ static int launch_fb_iteration(mvs_ctx *ctx, const float *M_in, const float *R0,
                                ptrdiff_t m_z, ptrdiff_t r1_z, ptrdiff_t flow_z)
 {
     hipStream_t st = ctx->stream;
-    if (m < 4 || ctx->hooks.fb_direct_box) {
+    if (m < 4) {
         dim3 g = g2(w, h);
         g.z = (unsigned)B;
         farneback_iteration_fused<<<g, 256, 0, st>>>(M_in, R0, R1, w, h, m, scale, flow, M_out, m_z, r1_z, flow_z);
@@ -1313,9 +1108,7 @@ static int launch_fb_iteration(mvs_ctx *ctx, const float *M_in, const float *R0,
         kernel<<<dim3(div_up(w, 64), div_up(h, ty), B), threads, lds, st>>>(M_in, R0, R1, w, h, m, scale, flow, M_out, m_z, r1_z, flow_z);
         return MVS_OK;
     };
-    // 64 x 16 tiles, 8 rows per thread of the vertical walk; (test hook MVS_FB_VARIANT=2: 4 rows per thread on 512 threads -- twice the
-    // wavefronts for the walk, measured SLOWER: 3.51 vs 3.16 ms per 1080p flow, its extra loads cost more than its occupancy buys)
-    if (tall && ctx->hooks.fb_variant == 2) return go(farneback_iteration_tiled<4, 4, 512>, 16, 4, 512, 4u);
+    // 64 x 16 tiles, 8 rows per thread of the vertical walk (4 rows on 512 threads measured slower: DESIGN.md section 6)
     if (tall) return go(farneback_iteration_tiled<8, 4, 256>, 16, 4, 256, 1u);
     return go(farneback_iteration_tiled<4, 2, 256>, 8, 2, 256, 2u);   // 64 x 8 tiles
 }
@@ -1324,11 +1117,10 @@ static int launch_fb_iteration(mvs_ctx *ctx, const float *M_in, const float *R0,
 // 1 + i = next frame i, P floats apart in F and blur, w*h apart in a level's I, 5 w*h apart in its R.
 struct FbBufs {
     const float *F;
-    float *tmp, *row3;            // the unfused A/B form only (MVS_FB_UNFUSED)
     float *blur, *I, *R;          // one level's worth each (n P, n P, 5 n P) -- or, prepared for all levels at once, `levels_floats` of them
     size_t blur_cap, i_cap, r_cap; // floats available behind the three pointers
     float *M, *M2;                // B x 5 P each (ping-pong of the fused iteration)
-    double *vs;                   // 5 P doubles, B == 1, unfused form only
+    double *vs;                   // 5 P doubles, B == 1, the three-launch iteration only (windows beyond FB_MAXM)
     float *flowA, *flowB;         // B x 2 P each
 };
 
@@ -1343,10 +1135,10 @@ static void fb_all_levels_floats(size_t P, size_t n, size_t &blur, size_t &I, si
 // cv::FarnebackOpticalFlow::calc, flags 0, for B flows against one previous frame (farneback_device: B = 1; mvs_process_frame's batched pass:
 // every side view of a main frame, blockIdx.z = flow).  flow_out: B x W*H*2.  Per pyramid level, coarse to fine:
 //   preparation  GaussianBlur of every full-resolution frame, resize to the level, polynomial expansion -- depends on the frames alone:
-//                for frames up to FB_BATCH_PREP_MAX_PIXELS all levels are prepared up front in THREE launches (round 6; 33 before);
+//                for frames up to FB_BATCH_PREP_MAX_PIXELS all levels are prepared up front in THREE launches (round 6; 33 before), larger
+//                frames level by level (prepare(): the same kernels' bodies on the same values);
 //   chain        the flow carried down + the first matrices (one launch; two before), then `iterations` fused iterations -- each needs
 //                the whole previous one.
-// The same kernels' bodies on the same values either way (MVS_FB_SERIAL_PREP=1 keeps the per-level preparation: A/B, tests).
 static int farneback_run(mvs_ctx *ctx, const FbBufs &b, int B, float *flow_out, int levels, double pyr_scale, int winsize, int iterations, int poly_n,
                          double poly_sigma)
 {
@@ -1355,9 +1147,9 @@ static int farneback_run(mvs_ctx *ctx, const FbBufs &b, int B, float *flow_out, 
     const ptrdiff_t sP = (ptrdiff_t)P;
     if (poly_n > 15) return fail(ctx, MVS_EINVAL, "farneback: poly_n %d too large", poly_n);
     const int m = winsize / 2;
-    // MVS_FB_UNFUSED=1 keeps the three-launch form of an iteration (A/B timing, single flows); windows beyond the LDS buffer use it too
-    const bool unfused = B == 1 && (ctx->hooks.fb_unfused || m > FB_MAXM);
-    if (B != 1 && m > FB_MAXM) return fail(ctx, MVS_EINVAL, "farneback (batched): window %d beyond the fused iteration's buffer", winsize);
+    // windows beyond the fused iteration's LDS buffer take the three-launch form, whose vertical sums need b.vs (single flows only)
+    const bool unfused = m > FB_MAXM;
+    if (unfused && (B != 1 || !b.vs)) return fail(ctx, MVS_EINVAL, "farneback (batched): window %d beyond the fused iteration's buffer", winsize);
     int lw[64], lh[64];
     double ls[64];
     {
@@ -1393,7 +1185,7 @@ static int farneback_run(mvs_ctx *ctx, const FbBufs &b, int B, float *flow_out, 
     FbLevels L;
     L.n = levels + 1;
     L.nimg = (int)nimg;
-    bool all_levels = !ctx->hooks.fb_unfused && !ctx->hooks.fb_serial_prep && P <= FB_BATCH_PREP_MAX_PIXELS && levels + 1 <= 11;
+    bool all_levels = P <= FB_BATCH_PREP_MAX_PIXELS && levels + 1 <= 11;
     if (all_levels) {
         size_t bo = 0, io = 0, ro = 0;
         int cmax = 0;
@@ -1434,22 +1226,12 @@ static int farneback_run(mvs_ctx *ctx, const FbBufs &b, int B, float *flow_out, 
         const int w = lw[k], h = lh[k];
         Taps taps;
         gaussian_taps(smooth_sz, sigma, taps.k);
-        dim3 gF = g2(W, H), gL = g2(w, h);
-        gF.z = gL.z = nimg;
-        if (ctx->hooks.fb_unfused) {
-            gauss_kernel<false><<<gF, 256, 0, st>>>(b.F, W, H, taps, smooth_sz, b.tmp, sP, sP);
-            gauss_kernel<true><<<gF, 256, 0, st>>>(b.tmp, W, H, taps, smooth_sz, b.blur, sP, sP);
-        } else {
-            const int c = smooth_sz / 2;
-            gauss_fused_kernel<<<dim3(div_up(W, 64), div_up(H, 16), nimg), 256, sizeof(float) * (size_t)(16 + 2 * c) * (128 + 2 * c), st>>>(b.F, W, H, taps, smooth_sz, b.blur, sP, sP);
-        }
+        const int c = smooth_sz / 2;
+        gauss_fused_kernel<<<dim3(div_up(W, 64), div_up(H, 16), nimg), 256, sizeof(float) * (size_t)(16 + 2 * c) * (128 + 2 * c), st>>>(b.F, W, H, taps, smooth_sz, b.blur, sP, sP);
+        dim3 gL = g2(w, h);
+        gL.z = nimg;
         resize_linear_kernel<1><<<gL, 256, 0, st>>>(b.blur, W, H, b.I, w, h, 1.f, 0, sP, sP);
-        if (ctx->hooks.fb_unfused) {
-            polyexp_vert<<<gL, 256, 0, st>>>(b.I, w, h, pt, b.row3, sP, 3 * sP);
-            polyexp_horiz<<<gL, 256, 0, st>>>(b.row3, w, h, pt, b.R, 3 * sP, 5 * sP);
-        } else {
-            polyexp_fused_kernel<<<dim3(div_up(w, 64), div_up(h, 16), nimg), 256, sizeof(float) * ((size_t)(16 + 2 * pt.n) * (64 + 2 * pt.n) + 3 * 16 * (size_t)(64 + 2 * pt.n)), st>>>(b.I, w, h, pt, b.R, sP, 5 * sP);
-        }
+        polyexp_fused_kernel<<<dim3(div_up(w, 64), div_up(h, 16), nimg), 256, sizeof(float) * ((size_t)(16 + 2 * pt.n) * (64 + 2 * pt.n) + 3 * 16 * (size_t)(64 + 2 * pt.n)), st>>>(b.I, w, h, pt, b.R, sP, 5 * sP);
     };
     int r;
     float *flow = nullptr, *prevflow = nullptr;
@@ -1491,7 +1273,7 @@ static size_t fb_work_floats(size_t P)
 {
     size_t blur = 2 * P, I = 2 * P, R = 10 * P;
     if (P <= FB_BATCH_PREP_MAX_PIXELS) fb_all_levels_floats(P, 2, blur, I, R);
-    return 10 * P + 2 * P + 6 * P + blur + I + R + 5 * P + 2 * P + 2 * P;   // vs, tmp, row3, blur, I, R, M, flowA, flowB
+    return 10 * P + blur + I + R + 5 * P + 2 * P + 2 * P;   // vs, blur, I, R, M, flowA, flowB
 }
 
 static int farneback_device(mvs_ctx *ctx, const float *f0, const float *f1, float *flow_out, float *arena, int levels,
@@ -1508,8 +1290,6 @@ static int farneback_device(mvs_ctx *ctx, const float *f0, const float *f1, floa
         p += count;
         return q;
     };
-    b.tmp = take(2 * P);
-    b.row3 = take(6 * P);
     b.blur_cap = 2 * P;
     b.i_cap = 2 * P;
     b.r_cap = 10 * P;
@@ -1538,37 +1318,14 @@ static int variational_device(mvs_ctx *ctx, const float *I0, const float *I1, fl
     for (size_t i = 0; i < sizeof(slots) / sizeof(slots[0]); i++) *slots[i] = arena + i * P;
     split_flow_kernel<<<g1(P), 256, 0, st>>>(flow, B.Wu, B.Wv, B.du, B.dv, P);
     warp_q5_kernel<<<g2(w, h), 256, 0, st>>>(I1, w, h, B.Wu, B.Wv, I0, A, B.Iz);
-    if (ctx->hooks.var_unfused) {   // (the A/B form keeps the seven separate launches too)
-        diff_kernel<false><<<g2(w, h), 256, 0, st>>>(A, w, h, B.Ix);
-        diff_kernel<true><<<g2(w, h), 256, 0, st>>>(A, w, h, B.Iy);
-        diff_kernel<false><<<g2(w, h), 256, 0, st>>>(B.Iz, w, h, B.Ixz);
-        diff_kernel<true><<<g2(w, h), 256, 0, st>>>(B.Iz, w, h, B.Iyz);
-        diff_kernel<false><<<g2(w, h), 256, 0, st>>>(B.Ix, w, h, B.Ixx);
-        diff_kernel<true><<<g2(w, h), 256, 0, st>>>(B.Ix, w, h, B.Ixy);
-        diff_kernel<true><<<g2(w, h), 256, 0, st>>>(B.Iy, w, h, B.Iyy);
-    } else {
-        var_derivatives_kernel<<<g2(w, h), 256, 0, st>>>(A, B.Iz, w, h, B);
-    }
-    const dim3 half(div_up((w + 1) / 2, 64), div_up(h, 4));
-    // MVS_VAR_UNFUSED=1 keeps the 13-launch form of a fixed-point iteration (A/B timing and the cross-check test)
-    const bool unfused = ctx->hooks.var_unfused;
+    var_derivatives_kernel<<<g2(w, h), 256, 0, st>>>(A, B.Iz, w, h, B);
     const int sor_iters = 5;
     if (2 * sor_iters > VT_HALO) return fail(ctx, MVS_EINVAL, "variational: %d SOR sweeps need a halo of %d", sor_iters, 2 * sor_iters);
     float *du_cur = B.du, *dv_cur = B.dv, *du_nxt = B.a11, *dv_nxt = B.a22;  // the fused form keeps coefficients on chip
     for (int fp = 0; fp < 5; fp++) {
-        if (unfused) {
-            var_data_term<<<g2(w, h), 256, 0, st>>>(B, w, h);
-            var_diffusivity<<<g2(w, h), 256, 0, st>>>(B, w, h);
-            var_smooth_gather<<<g2(w, h), 256, 0, st>>>(B, w, h);
-            for (int it = 0; it < sor_iters; it++) {
-                var_sor_pass<<<half, 256, 0, st>>>(B, w, h, 0);
-                var_sor_pass<<<half, 256, 0, st>>>(B, w, h, 1);
-            }
-        } else {
-            var_fixed_point_fused<<<dim3(div_up(w, VT_W), div_up(h, VT_H)), VT_THREADS, 0, st>>>(B, du_cur, dv_cur, du_nxt, dv_nxt, w, h, sor_iters);
-            std::swap(du_cur, du_nxt);
-            std::swap(dv_cur, dv_nxt);
-        }
+        var_fixed_point_fused<<<dim3(div_up(w, VT_W), div_up(h, VT_H)), VT_THREADS, 0, st>>>(B, du_cur, dv_cur, du_nxt, dv_nxt, w, h, sor_iters);
+        std::swap(du_cur, du_nxt);
+        std::swap(dv_cur, dv_nxt);
     }
     B.du = du_cur;
     B.dv = dv_cur;
@@ -1607,63 +1364,35 @@ static int flow_prepare(mvs_ctx *ctx, FlowBufs &b, int use_farneback, bool flow_
 // flow.cpp:19-42 on the buffers of `b`: inputs b.p8 / b.n8 (u8), output b.out4.  Everything between is a fixed
 // sequence of kernels on fixed buffers.
 // flow_only: stop after the flow (b.flow2): the variance channel and the packing are the caller's (flow_variance_batch_device)
+// Eager launches.  Rounds 2-3 replayed this sequence as a captured HIP graph; round 4 found that a graph instantiated before some first-time
+// event elsewhere in the process (the first mvs_poisson_surface call: rocFFT's run-time kernels, new code objects) replays with WRONG
+// results afterwards -- silently, deterministically within the process, differently from process to process --
+// and that on this ROCm the eager launches are no slower (mvs_process_frame 1.69 ms against 1.95 with the graphs).
 static int flow_run(mvs_ctx *ctx, const FlowBufs &b, int use_farneback, bool flow_only = false)
 {
     const int W = ctx->W, H = ctx->H;
     const size_t P = (size_t)W * H;
     hipStream_t st = ctx->stream;
-    auto enqueue = [&]() -> int {
-        u8_to_f32_pair_kernel<<<g1(P), 256, 0, st>>>(b.p8, b.n8, b.f0, b.f1, P);
-        int r;
-        if (use_farneback) {
-            const double poly_sigma = (H + W) / 1000.0;  // flow.cpp:24-25
-            const int winsize = (H + W) / 100, poly_n = poly_sigma < 1.5 ? 5 : 7;
-            if ((r = farneback_device(ctx, b.f0, b.f1, b.flow2, b.arena, 10, 0.8, winsize, 7, poly_n, poly_sigma))) return r;
-        } else {
-            if (ctx->hooks.flow_graph_kernel_memset)
-                zero_f32_kernel<<<g1(2 * P), 256, 0, st>>>(b.flow2, 2 * P);
-            else
-                MVS_HIP(ctx, hipMemsetAsync(b.flow2, 0, sizeof(float) * 2 * P, st));  // flow.cpp:31 (uninitialised there), A-11
-            if ((r = variational_device(ctx, b.f0, b.f1, b.flow2, b.arena))) return r;
-        }
-        if (flow_only) {
-            MVS_HIP(ctx, hipGetLastError());
-            return MVS_OK;
-        }
-        if ((r = remap_device(ctx, b.flow2, 2, b.n8, b.r8))) return r;  // flow.cpp:34
-        if ((r = compare_device(ctx, b.p8, b.r8, b.var))) return r;
-        pack_flow4<<<g1(P), 256, 0, st>>>(b.flow2, b.var, b.out4, P);
+    ProfileScope ps(ctx, MVS_K_FLOW);
+    u8_to_f32_pair_kernel<<<g1(P), 256, 0, st>>>(b.p8, b.n8, b.f0, b.f1, P);
+    int r;
+    if (use_farneback) {
+        const double poly_sigma = (H + W) / 1000.0;  // flow.cpp:24-25
+        const int winsize = (H + W) / 100, poly_n = poly_sigma < 1.5 ? 5 : 7;
+        if ((r = farneback_device(ctx, b.f0, b.f1, b.flow2, b.arena, 10, 0.8, winsize, 7, poly_n, poly_sigma))) return r;
+    } else {
+        MVS_HIP(ctx, hipMemsetAsync(b.flow2, 0, sizeof(float) * 2 * P, st));  // flow.cpp:31 (uninitialised there), A-11
+        if ((r = variational_device(ctx, b.f0, b.f1, b.flow2, b.arena))) return r;
+    }
+    if (flow_only) {
         MVS_HIP(ctx, hipGetLastError());
         return MVS_OK;
-    };
-    // Eager launches.  Rounds 2-3 replayed this sequence as a hipGraph; round 4 found that a graph instantiated before some first-time
-    // event elsewhere in the process (the first mvs_poisson_surface call: rocFFT's run-time kernels, new code objects) replays with WRONG
-    // results afterwards -- silently, deterministically within the process, differently from process to process --
-    // and that on this ROCm the eager launches are no slower (mvs_process_frame 1.69 ms against 1.95 with the graphs).
-    ProfileScope ps(ctx, MVS_K_FLOW);
-    if (ctx->hooks.flow_graph) {  // test hook: the graph replay of rounds 2-3, kept for the reproducer of what round 4 found (tools/graph_repro.py)
-        const int gi = use_farneback ? 1 : 0;
-        if (ctx->flow_graph[gi] && ctx->flow_graph_arena[gi] != ctx->flow_arena.ptr) {
-            (void)hipGraphExecDestroy(ctx->flow_graph[gi]);
-            ctx->flow_graph[gi] = nullptr;
-        }
-        if (!ctx->flow_graph[gi]) {
-            hipGraph_t graph = nullptr;
-            MVS_HIP(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            const int r = enqueue();
-            const hipError_t e = hipStreamEndCapture(st, &graph);
-            if (r != MVS_OK || e != hipSuccess || !graph || hipGraphInstantiate(&ctx->flow_graph[gi], graph, nullptr, nullptr, 0) != hipSuccess) {
-                ctx->flow_graph[gi] = nullptr;
-                if (graph) (void)hipGraphDestroy(graph);
-                return fail(ctx, MVS_EHIP, "MVS_FLOW_GRAPH: capture / instantiation failed");
-            }
-            (void)hipGraphDestroy(graph);
-            ctx->flow_graph_arena[gi] = ctx->flow_arena.ptr;
-        }
-        MVS_HIP(ctx, hipGraphLaunch(ctx->flow_graph[gi], st));
-        return MVS_OK;
     }
-    return enqueue();
+    if ((r = remap_device(ctx, b.flow2, 2, b.n8, b.r8))) return r;  // flow.cpp:34
+    if ((r = compare_device(ctx, b.p8, b.r8, b.var))) return r;
+    pack_flow4<<<g1(P), 256, 0, st>>>(b.flow2, b.var, b.out4, P);
+    MVS_HIP(ctx, hipGetLastError());
+    return MVS_OK;
 }
 
 // ---- calculateFlow (Farneback) of SEVERAL next-frames against one previous frame in one pass --------------------------------
@@ -1693,8 +1422,6 @@ static FlowBatchBufs flow_batch_layout(float *arena, size_t P, int B)
     b.F = take(n * P);
     b.fb.F = b.F;
     b.fb.vs = nullptr;
-    b.fb.tmp = take(n * P);
-    b.fb.row3 = take(n * 3 * P);
     b.fb.blur_cap = n * P;
     b.fb.i_cap = n * P;
     b.fb.r_cap = n * 5 * P;
@@ -1797,17 +1524,6 @@ int flow_variance_batch_device(mvs_ctx *ctx, const uint8_t *prev8, const uint8_t
 using namespace mvs;
 
 extern "C" {
-
-// test hook (not in mvs.h; tools/graph_repro.py): the first `count` floats of calculateFlow's work arena, as the last mvs_flow left them
-int mvs_test_flow_arena(mvs_ctx *ctx, float *out, size_t count)
-{
-    if (!ctx || !out) return MVS_EINVAL;
-    if (!ctx->flow_arena.ptr || count * sizeof(float) > ctx->flow_arena.bytes) return fail(ctx, MVS_ESTATE, "mvs_test_flow_arena: the arena holds %zu bytes", ctx->flow_arena.bytes);
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    MVS_HIP(ctx, hipMemcpyAsync(out, ctx->flow_arena.ptr, count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return MVS_OK;
-}
 
 int mvs_flow(mvs_ctx *ctx, const uint8_t *prev_hw, const uint8_t *next_hw, int use_farneback, float *out_hw4)
 {

@@ -39,7 +39,7 @@ Hooks read_hooks()
     h.enabled = flag("MVS_TEST_HOOKS");
     if (!h.enabled) {
         // production: nothing else is looked at -- but a hook variable that is SET and ignored is a silent A/B with two equal arms
-        // (tools/time_process_frame.py under MVS_SERIAL_FLOWS=1), so say so once per process.  MVS_DEVICE belongs to the C++
+        // (ADVICE r05 found a timing tool run that way), so say so once per process.  MVS_DEVICE belongs to the C++
         // host mirror (host/render_hip.cpp), MVS_BUILD_VARIANT / MVS_BENCH_* to the Python harness: not library hooks.
         static std::once_flag warned;
         std::call_once(warned, [] {
@@ -66,15 +66,6 @@ Hooks read_hooks()
     h.filter_timing = present("MVS_FILTER_TIMING");
     h.filter_sorted_lists = number("MVS_FILTER_SORTED_LISTS", -1);
     h.filter_max_rounds = number("MVS_FILTER_MAX_ROUNDS", 2048);
-    h.serial_flows = present("MVS_SERIAL_FLOWS");
-    h.fb_lanes = present("MVS_FB_LANES");
-    h.fb_unfused = present("MVS_FB_UNFUSED");
-    h.fb_serial_prep = present("MVS_FB_SERIAL_PREP");
-    h.var_unfused = present("MVS_VAR_UNFUSED");
-    h.fb_direct_box = present("MVS_FB_DIRECT_BOX");
-    h.flow_graph = present("MVS_FLOW_GRAPH");
-    h.flow_graph_kernel_memset = number("MVS_FLOW_GRAPH", 0) == 2;
-    h.fb_variant = number("MVS_FB_VARIANT", 0);
     h.onecall_bands = number("MVS_ONECALL_BANDS", 0);
     h.onecall_first_permille = number("MVS_ONECALL_FIRST", 0);
     h.raster_bins = number("MVS_RASTER_BINS", -1);

@@ -139,16 +139,14 @@ static int process_frame_impl(mvs_ctx *ctx, const float main_cam[16], const uint
     // The flows of the side views depend only on (main frame, mixed_i): each runs in a lane of its own while the main stream goes on
     // rasterising the next view; a flow is a chain of small kernels that fills 150 of 256 CUs at best, so up to four of them overlap.
     // Everything joins before the batched variance pass and triangulatePixels.
-    const bool serial = ctx->hooks.serial_flows;  // A/B: all flows in the main stream, as before
     // Farneback (-f): the flows of all side views in ONE pass after the last mixed image (every launch covers all of them; what
     // depends on the main frame alone is computed once) -- a Farneback flow is ~150 launches of a few microseconds, and concurrency
-    // between lanes does not buy what sharing the launches does.  MVS_FB_LANES=1 keeps the per-view chains on the lanes (A/B).
-    const bool fb_lanes = ctx->hooks.fb_lanes;
-    const bool fb_batch = use_farneback && nside > 0 && !serial && !fb_lanes;
+    // between lanes does not buy what sharing the launches does.
+    const bool fb_batch = use_farneback && nside > 0;
     // The LAST side view's flow stays on the main stream: after that view's side pass the main stream has nothing to do until the flows join, and HIP
     // serves a process's streams from four hardware queues -- main stream + four lanes made the fourth lane share a queue with another one, and its flow
     // started when that one's had finished (200 us of a 1.5 ms call at 640 x 480 with four side views, profiles/r06).
-    const int nlanes = (serial || fb_batch) ? 0 : std::max(0, std::min(nside - 1, (int)mvs_ctx::kFlowLanes));
+    const int nlanes = fb_batch ? 0 : std::max(0, std::min(nside - 1, (int)mvs_ctx::kFlowLanes));
     for (int l = 0; l < nlanes; l++)
         if (!ctx->lanes[l].stream) MVS_HIP(ctx, hipStreamCreateWithFlags(&ctx->lanes[l].stream, hipStreamNonBlocking));
     while ((int)ctx->lane_events.size() < 2 * nside) {

@@ -1,8 +1,7 @@
 """mvs_process_frame (recon.cpp:65-117 for one main frame: depth, 4 x (projected, mixBackground, calculateFlow), triangulatePixels) on the zatisi cameras at
-640 x 480, both flow algorithms; and the same under MVS_SERIAL_FLOWS=1 / MVS_FB_LANES=1 when those are set in the environment.
+640 x 480, both flow algorithms.
 python tools/time_process_frame.py [1080p]     (1080p: a synthetic scene at 1920 x 1080 with 4 side views, tests/test_pipeline_gpu.py's, instead of the zatisi cameras)"""
 import os, sys, time
-os.environ.setdefault("MVS_TEST_HOOKS", "1")   # the A/B variables above are environment hooks: read only under the master switch
 import torch  # noqa: F401 (HIP runtime first)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mesh-reconstruction_amd", "python")); sys.path.insert(0, os.path.join(ROOT, "tests"))
