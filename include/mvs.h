@@ -302,6 +302,32 @@ void *mvs_fuse_points_device(mvs_ctx *ctx); /* rows of the last mvs_fuse_depth, 
  * out[32..35] = camera centre (x, y, z, 1): the null vector of P's rows x, y, w, dehomogenised in double, rounded once */
 int mvs_depth_slot_matrices(const mvs_ctx *ctx, int slot, float out[36]);
 
+/* ---- TSDF fusion: every stored depth map votes into one truncated signed distance volume, meshed at its zero level set ----------
+ * (csrc/tsdf.hip; Curless & Levoy 1996.)  The context owns one cubic volume of G^3 nodes, G = 16..512: node (i, j, k)
+ * at (ox + h i, oy + h j, oz + h k), an f32 sum and an i32 count per node in the order (k G + j) G + i, 8 bytes per node.  mvs_tsdf_volume
+ * sizes and zeroes it (again: clears it); the depth store does not touch it.  mvs_tsdf_integrate adds the listed slots' maps in list order,
+ * asynchronous and stream-ordered like mvs_sweep_run; a slot listed twice counts twice, and a list split over several calls gives the same
+ * bytes as one call.  All f32, one rounding per operation, no contraction; inv_tau = 1 / truncation rounded once on the host:
+ *   1 per listed slot, a w-map: pixel valid by fusion rule 1 (with max_cost) and w = (P (X, 1)).w > 0 with X from rule 2: w, else NaN
+ *   2 per node (x = ox + h i, ... each a product then a sum) and slot: q_r = P[r][0] x + ((P[r][1] y + P[r][2] z) + P[r][3]), r = 0, 1, 3;
+ *     no update unless q_w > 0
+ *   3 inv = 1 / q_w, u = (q_x inv + 1) (W 0.5) - 0.5, v = (1 - q_y inv) (H 0.5) - 0.5; pixel (floor(v + 0.5), floor(u + 0.5)), tested
+ *     against the frame as floats; no update outside it or where the w-map holds NaN
+ *   4 t = (wd - q_w) inv_tau (positive in front of the surface, on the camera's side); when t >= -1: sum += min(t, 1), count += 1
+ *   5 mvs_tsdf_surface: F = sum / (float)count where count >= min_observations, else 1; a cell is meshed when all 8 corners have
+ *     count >= min_observations; surface nets at iso 0 as mvs_poisson_surface meshes chi, faces along +grad F (toward the cameras).
+ *     The surface has grid = {G, origin, h}, iso 0, spacing h (mvs_surface_spacing), ratio_kept 1, support 0, no chi or splat; the
+ *     mvs_surface_* calls all work on it.  An empty volume gives 0 vertices and 0 faces.
+ * mvs_tsdf_fetch synchronises and downloads the fields (diagnostic).  Errors: MVS_EINVAL for a NULL ctx, out or slots, G outside 16..512,
+ * a non-finite origin, a spacing or truncation not finite and > 0, nslots < 1, a slot outside the store, a negative or NaN max_cost,
+ * min_observations < 1; MVS_ESTATE before mvs_tsdf_volume, for an unfilled slot, or a finite max_cost when a slot was stored without cost.
+ * max_cost = INFINITY: costs are not read.  MVS_K_TSDF times mvs_tsdf_integrate's launches. */
+struct mvs_surface;
+int mvs_tsdf_volume(mvs_ctx *ctx, int nodes_per_axis /* 16..512 */, const float origin3[3], float node_spacing, float truncation);
+int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cost /* INFINITY: costs not read */);
+int mvs_tsdf_fetch(mvs_ctx *ctx, float *sdf_sum /* G^3, nullable */, int32_t *count /* G^3, nullable */);
+int mvs_tsdf_surface(mvs_ctx *ctx, int min_observations /* >= 1 */, struct mvs_surface **out);
+
 /* ---- one main view on several GPUs of one node (SURVEY.md section 8b "multi-GPU", 8e, north_star) -----------------------------
  * A communicator owns one context per listed device and one RCCL communicator across them (librccl is loaded when the first
  * communicator is created; the library has no link dependency on it).  mvs_sweep_sharded runs ONE main view on all of them, one host
@@ -382,6 +408,7 @@ int mvs_comm_device(const mvs_comm *comm, int rank);
 #define MVS_K_PROJECT 4
 #define MVS_K_FLOW 5
 #define MVS_K_FUSE 6 /* mvs_fuse_depth: count pass, scan, row pass */
+#define MVS_K_TSDF 7 /* mvs_tsdf_integrate: w-map passes and integration launches */
 #define MVS_K_COUNT 8
 int mvs_profile_enable(mvs_ctx *ctx, int on);
 /* synchronises, then returns summed elapsed ms and launch count per kernel class since the last reset */

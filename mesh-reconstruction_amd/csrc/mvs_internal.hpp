@@ -157,6 +157,12 @@ struct mvs_ctx {
     std::vector<DepthSlot> dstore;
     mvs::DevBuf fuse_rows, fuse_counts, fuse_scan;  // rows of the last mvs_fuse_depth; per-segment keep counts and their offsets; scan scratch
     bool fuse_have_rows = false;
+    // TSDF volume (tsdf.hip: mvs_tsdf_volume / mvs_tsdf_integrate / mvs_tsdf_surface): G^3 f32 sums then G^3 i32 counts; the w-maps of one
+    // integration launch; the field and support mask mvs_tsdf_surface meshes.  tsdf_G = 0: no volume yet.
+    mvs::DevBuf tsdf_vol, tsdf_wmaps, tsdf_work;
+    int tsdf_G = 0;
+    float tsdf_origin[3] = {0.f, 0.f, 0.f};
+    float tsdf_h = 0.f, tsdf_inv_tau = 0.f;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

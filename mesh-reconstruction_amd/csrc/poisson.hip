@@ -544,6 +544,61 @@ bool ensure_plans(int G, const char **why)
 
 }  // namespace
 
+// step 4 of the header: surface nets over a device field (surface_internal.hpp).  Shared with csrc/tsdf.hip (mvs_tsdf_surface).
+int surface_nets_device(const SurfaceGrid &g, const float *chi, float iso, const unsigned char *support, ihipStream_t *stream, mvs_surface *res,
+                        const char *who, std::string &why)
+{
+    hipStream_t st = stream;
+    const size_t N3 = (size_t)g.G * g.G * g.G;
+    const int C = g.G - 1;
+    const size_t C3 = (size_t)C * C * C;
+    DevBuf d_flag, d_index, d_cell_index, d_tmp, d_vertices, d_faces, d_patches, d_cases;
+    size_t tmp_bytes = 0;
+#define MESH_TRY(cond, code, text) do { if (!(cond)) { why = std::string(who) + ": " + (text); return (code); } } while (0)
+    try {
+        MESH_TRY(d_flag.alloc(3 * N3 * 4) && d_index.alloc((3 * N3 + 1) * 4) && d_cell_index.alloc((C3 + 1) * 4), MVS_ENOMEM, "device allocation failed");
+        // vertices
+        int *flag = d_flag.as<int>(), *cell_index = d_cell_index.as<int>();
+        uint32_t patch_table[256];
+        cell_patch_table(patch_table);
+        MESH_TRY(d_patches.alloc(sizeof(patch_table)) && d_cases.alloc(C3), MVS_ENOMEM, "device allocation failed");
+        MESH_TRY(hipMemcpyAsync(d_patches.p, patch_table, sizeof(patch_table), hipMemcpyHostToDevice, st) == hipSuccess, MVS_EHIP, "upload failed");
+        const uint32_t *patches = d_patches.as<uint32_t>();
+        const unsigned char *cases = d_cases.as<unsigned char>();
+        cell_flags_kernel<<<(unsigned)((C3 + 255) / 256), 256, 0, st>>>(g, chi, iso, support, patches, flag, d_cases.as<unsigned char>());
+        MESH_TRY(hipMemsetAsync(flag + C3, 0, 4, st) == hipSuccess && scan(flag, cell_index, C3 + 1, st, d_tmp, tmp_bytes), MVS_EHIP, "scan failed");
+        int nv = 0;
+        MESH_TRY(hipMemcpyAsync(&nv, cell_index + C3, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess, MVS_EHIP, "count failed");
+        MESH_TRY(d_vertices.alloc((size_t)nv * 16), MVS_ENOMEM, "device allocation failed");
+        if (nv > 0) cell_vertices_kernel<<<(unsigned)((C3 + 255) / 256), 256, 0, st>>>(g, chi, iso, flag, cell_index, patches, cases, d_vertices.as<float>());
+        res->vertices.resize((size_t)nv * 4);
+        if (nv > 0) MESH_TRY(hipMemcpyAsync(res->vertices.data(), d_vertices.p, (size_t)nv * 16, hipMemcpyDeviceToHost, st) == hipSuccess, MVS_EHIP, "download failed");
+        // faces (the cell flags are overwritten by the edge flags: the vertex kernel above is ordered before on the stream)
+        int *index = d_index.as<int>();
+        edge_flags_kernel<<<(unsigned)((3 * N3 + 255) / 256), 256, 0, st>>>(g, chi, iso, support, flag);
+        {
+            // flag has 3 N3 entries; the scan needs one more (the total): d_flag was sized 3 N3, so scan into index[0 .. 3 N3] with the
+            // total computed from the last offset + last flag
+            MESH_TRY(scan(flag, index, 3 * N3, st, d_tmp, tmp_bytes), MVS_EHIP, "scan failed");
+        }
+        int last_off = 0, last_flag = 0;
+        MESH_TRY(hipMemcpyAsync(&last_off, index + 3 * N3 - 1, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                   hipMemcpyAsync(&last_flag, flag + 3 * N3 - 1, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess,
+               MVS_EHIP, "count failed");
+        const int nq = last_off + last_flag;
+        MESH_TRY(d_faces.alloc((size_t)nq * 24), MVS_ENOMEM, "device allocation failed");
+        if (nq > 0) edge_faces_kernel<<<(unsigned)((3 * N3 + 255) / 256), 256, 0, st>>>(g, chi, iso, support, flag, index, cell_index, patches, cases, d_faces.as<int>());
+        res->faces.resize((size_t)nq * 6);
+        if (nq > 0) MESH_TRY(hipMemcpyAsync(res->faces.data(), d_faces.p, (size_t)nq * 24, hipMemcpyDeviceToHost, st) == hipSuccess, MVS_EHIP, "download failed");
+        MESH_TRY(hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess, MVS_EHIP, "a kernel failed");
+    } catch (...) {  // a host vector could not grow: no exception crosses the C boundary
+        why = std::string(who) + ": host allocation failed";
+        return MVS_ENOMEM;
+    }
+#undef MESH_TRY
+    return MVS_OK;
+}
+
 // test hook (not in mvs.h; tests/test_meshing_cpu.py): the patch table of the surface nets, as the kernels receive it (host code, no GPU)
 extern "C" int mvs_test_cell_patch_table(uint32_t out[256])
 {
@@ -711,8 +766,6 @@ extern "C" int mvs_poisson_surface_ex(const float *points, const float *normals,
     g.oy = (float)(0.5 * (lo[1] + hi[1]) - 0.5 * box);
     g.oz = (float)(0.5 * (lo[2] + hi[2]) - 0.5 * box);
     const size_t N3 = (size_t)g.G * g.G * g.G, S3 = (size_t)g.G * g.G * (g.G / 2 + 1);
-    const int C = g.G - 1;
-    const size_t C3 = (size_t)C * C * C;
 
     mvs_surface *res = new (std::nothrow) mvs_surface;
     if (!res) return fail(MVS_ENOMEM, "mvs_poisson_surface: host allocation failed");
@@ -720,14 +773,13 @@ extern "C" int mvs_poisson_surface_ex(const float *points, const float *normals,
     res->normal_scale_log2 = nscale_log2;
     res->spacing = (float)spacing;
     res->ratio_kept = ratio_kept;
-    DevBuf d_fix, d_real, d_spec, d_flag, d_index, d_cell_index, d_tmp, d_samples, d_vertices, d_faces, d_mask, d_patches, d_cases;
-    size_t tmp_bytes = 0;
+    DevBuf d_fix, d_real, d_spec, d_samples, d_mask;
+    std::string mesh_why;
     int rc = MVS_OK;
     const char *msg = "";
 #define PS_TRY(cond, code, text) do { if (!(cond)) { rc = (code); msg = (text); goto done; } } while (0)
     try {
-        PS_TRY(d_fix.alloc(4 * N3 * sizeof(fix_t)) && d_real.alloc(3 * N3 * 4) && d_spec.alloc(3 * S3 * 8) &&
-                   d_flag.alloc(3 * N3 * 4) && d_index.alloc((3 * N3 + 1) * 4) && d_cell_index.alloc((C3 + 1) * 4) && d_samples.alloc((size_t)n * 4),
+        PS_TRY(d_fix.alloc(4 * N3 * sizeof(fix_t)) && d_real.alloc(3 * N3 * 4) && d_spec.alloc(3 * S3 * 8) && d_samples.alloc((size_t)n * 4),
                MVS_ENOMEM, "mvs_poisson_surface: device allocation failed");
         PS_TRY(hipMemsetAsync(d_fix.p, 0, 4 * N3 * sizeof(fix_t), st) == hipSuccess, MVS_EHIP, "mvs_poisson_surface: clearing the grid failed");
         fix_t *vx = d_fix.as<fix_t>(), *vy = vx + N3, *vz = vy + N3, *wt = vz + N3;
@@ -770,39 +822,10 @@ extern "C" int mvs_poisson_surface_ex(const float *points, const float *normals,
             PS_TRY(hipGetLastError() == hipSuccess, MVS_EHIP, "mvs_poisson_surface: support mask launch failed");
             support = m1;
         }
-        // vertices
-        int *flag = d_flag.as<int>(), *cell_index = d_cell_index.as<int>();
-        uint32_t patch_table[256];
-        cell_patch_table(patch_table);
-        PS_TRY(d_patches.alloc(sizeof(patch_table)) && d_cases.alloc(C3), MVS_ENOMEM, "mvs_poisson_surface: device allocation failed");
-        PS_TRY(hipMemcpyAsync(d_patches.p, patch_table, sizeof(patch_table), hipMemcpyHostToDevice, st) == hipSuccess, MVS_EHIP, "mvs_poisson_surface: upload failed");
-        const uint32_t *patches = d_patches.as<uint32_t>();
-        const unsigned char *cases = d_cases.as<unsigned char>();
-        cell_flags_kernel<<<(unsigned)((C3 + 255) / 256), 256, 0, st>>>(g, chi, iso, support, patches, flag, d_cases.as<unsigned char>());
-        PS_TRY(hipMemsetAsync(flag + C3, 0, 4, st) == hipSuccess && scan(flag, cell_index, C3 + 1, st, d_tmp, tmp_bytes), MVS_EHIP, "mvs_poisson_surface: scan failed");
-        int nv = 0;
-        PS_TRY(hipMemcpyAsync(&nv, cell_index + C3, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess, MVS_EHIP, "mvs_poisson_surface: count failed");
-        PS_TRY(d_vertices.alloc((size_t)nv * 16), MVS_ENOMEM, "mvs_poisson_surface: device allocation failed");
-        if (nv > 0) cell_vertices_kernel<<<(unsigned)((C3 + 255) / 256), 256, 0, st>>>(g, chi, iso, flag, cell_index, patches, cases, d_vertices.as<float>());
-        res->vertices.resize((size_t)nv * 4);
-        if (nv > 0) PS_TRY(hipMemcpyAsync(res->vertices.data(), d_vertices.p, (size_t)nv * 16, hipMemcpyDeviceToHost, st) == hipSuccess, MVS_EHIP, "mvs_poisson_surface: download failed");
-        // faces (the cell flags are overwritten by the edge flags: the vertex kernel above is ordered before on the stream)
-        int *index = d_index.as<int>();
-        edge_flags_kernel<<<(unsigned)((3 * N3 + 255) / 256), 256, 0, st>>>(g, chi, iso, support, flag);
         {
-            // flag has 3 N3 entries; the scan needs one more (the total): d_flag was sized 3 N3, so scan into index[0 .. 3 N3] with the
-            // total computed from the last offset + last flag
-            PS_TRY(scan(flag, index, 3 * N3, st, d_tmp, tmp_bytes), MVS_EHIP, "mvs_poisson_surface: scan failed");
+            const int mrc = surface_nets_device(g, chi, iso, support, st, res, "mvs_poisson_surface", mesh_why);
+            PS_TRY(mrc == MVS_OK, mrc, mesh_why.c_str());
         }
-        int last_off = 0, last_flag = 0;
-        PS_TRY(hipMemcpyAsync(&last_off, index + 3 * N3 - 1, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                   hipMemcpyAsync(&last_flag, flag + 3 * N3 - 1, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess,
-               MVS_EHIP, "mvs_poisson_surface: count failed");
-        const int nq = last_off + last_flag;
-        PS_TRY(d_faces.alloc((size_t)nq * 24), MVS_ENOMEM, "mvs_poisson_surface: device allocation failed");
-        if (nq > 0) edge_faces_kernel<<<(unsigned)((3 * N3 + 255) / 256), 256, 0, st>>>(g, chi, iso, support, flag, index, cell_index, patches, cases, d_faces.as<int>());
-        res->faces.resize((size_t)nq * 6);
-        if (nq > 0) PS_TRY(hipMemcpyAsync(res->faces.data(), d_faces.p, (size_t)nq * 24, hipMemcpyDeviceToHost, st) == hipSuccess, MVS_EHIP, "mvs_poisson_surface: download failed");
         if (keep_fields) {
             res->chi.resize(N3);
             res->splat.resize(4 * N3);

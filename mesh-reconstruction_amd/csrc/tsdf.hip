@@ -1,0 +1,284 @@
+// tsdf.hip -- TSDF fusion (include/mvs.h "TSDF fusion"): every stored depth map votes a truncated signed distance
+// along its own rays into one G^3 volume owned by the context; mvs_tsdf_surface meshes the averaged field's zero level set with Poisson's
+// surface nets (csrc/poisson.hip: surface_nets_device).
+//
+// mvs_tsdf_integrate runs per chunk of up to kTsdfChunk listed slots, in list order, two launches:
+//   tsdf_wmap_kernel       one thread per pixel and slot of the chunk: the slot's linear depth w where the stored pixel is valid (fusion
+//                          rules 1 and 2, csrc/depth_rules.hpp, exactly as mvs_fuse_depth reads it), NaN elsewhere;
+//   tsdf_integrate_kernel  one thread per node, i fastest: with blockDim 256 = 64 x 4 every wavefront is one run of 64 nodes of one
+//                          (j, k) row, so the bracket (P[r][1] y + P[r][2] z) + P[r][3] is wave-uniform and a wave's depth gathers land on a
+//                          few neighbouring image lines.  The chunk's rows x, y, w of P travel by value in the kernel arguments (as
+//                          FuseArgs does); the node's (sum, count) is read once, updated by the chunk's slots in list order, written once.
+//                          No atomics, no LDS: the result is the same bytes however the list is split into calls or chunks.
+// mvs_tsdf_surface: tsdf_field_kernel turns (sum, count) into F and the cell support mask, then the shared mesher runs on ctx->stream.
+//
+// Arithmetic: f32, one rounding per operation, no contraction (the library builds with -ffp-contract=off; the pixel centres' fmaf is the
+// sweep's and is written out); tests/tsdf_mirror.py restates it in numpy, bit for bit.
+#include "depth_rules.hpp"
+#include "mvs_internal.hpp"
+#include "surface_internal.hpp"
+
+#include <cmath>
+#include <new>
+#include <string>
+
+namespace mvs {
+
+namespace {
+
+constexpr int kTsdfChunk = 16;               // slots per integration launch
+constexpr int kTsdfMinG = 16, kTsdfMaxG = 512;
+constexpr int kTsdfTX = 64, kTsdfTY = 4;     // integration block: 64 nodes along i x 4 rows along j
+constexpr int kTsdfBatch = 8;                // gathers in flight per thread
+
+struct WmapArgs {
+    const float *depth[kTsdfChunk];
+    const float *cost[kTsdfChunk];           // null unless max_cost is finite
+    float Pw[kTsdfChunk][4];                 // row w of P
+    float Pi[kTsdfChunk][16];
+    float *wmap;                             // the chunk's maps, W*H apart
+    int W, H, use_cost;
+    float invW, invH, max_cost;
+};
+
+struct IntegrateArgs {
+    const float *wmap;                       // the chunk's w-maps, W*H apart, in list order
+    float P[kTsdfChunk][12];                 // rows x, y, w of P
+    int n, W, H, G;
+    float ox, oy, oz, h, halfW, halfH, inv_tau;
+};
+
+__global__ __launch_bounds__(256) void tsdf_wmap_kernel(const WmapArgs a)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (p >= a.W * a.H) return;
+    const int r = p / a.W, c = p - r * a.W;
+    float w = __builtin_nanf("");
+    const float z = a.depth[s][p];
+    if (depth_valid(z, a.cost[s], (size_t)p, a.use_cost, a.max_cost)) {
+        const float xn = __builtin_fmaf((float)(2 * c + 1), a.invW, -1.0f);
+        const float yn = __builtin_fmaf(-(float)(2 * r + 1), a.invH, 1.0f);
+        const float ws = prow(a.Pw[s], 0, unproject(a.Pi[s], xn, yn, z));
+        if (ws > 0.f) w = ws;
+    }
+    a.wmap[(size_t)s * a.W * a.H + p] = w;
+}
+
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs a, float *__restrict__ sum, int *__restrict__ count)
+{
+    const int i = blockIdx.x * kTsdfTX + (int)(threadIdx.x & (kTsdfTX - 1));
+    const int j = blockIdx.y * kTsdfTY + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kTsdfTX));  // (one wave = one row: uniform)
+    const int k = blockIdx.z;
+    if (i >= a.G || j >= a.G) return;
+    const float x = a.ox + a.h * (float)i, y = a.oy + a.h * (float)j, z = a.oz + a.h * (float)k;
+    const size_t node = ((size_t)k * a.G + j) * a.G + i;
+    const size_t P = (size_t)a.W * a.H;
+    float s = sum[node];
+    int c = count[node];
+    // kTsdfBatch slots at a time: first every gather of the batch is issued, then the updates run in list order (a slot with nothing to
+    // say -- behind the camera, outside the frame, no depth there -- reads as NaN), so a wave waits for one batch of loads, not for each
+    for (int e0 = 0; e0 < a.n; e0 += kTsdfBatch) {
+        float qw[kTsdfBatch], wd[kTsdfBatch];
+#pragma unroll
+        for (int b = 0; b < kTsdfBatch; b++) {
+            wd[b] = __builtin_nanf("");
+            qw[b] = 0.f;
+            if (e0 + b >= a.n) continue;
+            const float *M = a.P[e0 + b];
+            qw[b] = M[8] * x + ((M[9] * y + M[10] * z) + M[11]);
+            if (!(qw[b] > 0.f)) continue;
+            const float qx = M[0] * x + ((M[1] * y + M[2] * z) + M[3]);
+            const float qy = M[4] * x + ((M[5] * y + M[6] * z) + M[7]);
+            const float inv = 1.0f / qw[b];
+            const float u = (qx * inv + 1.0f) * a.halfW - 0.5f;
+            const float v = (1.0f - qy * inv) * a.halfH - 0.5f;
+            const float fc = floorf(u + 0.5f), fr = floorf(v + 0.5f);
+            if (!(fc >= 0.f && fc < (float)a.W && fr >= 0.f && fr < (float)a.H)) continue;  // (NaN fails too)
+            wd[b] = a.wmap[P * (e0 + b) + (size_t)((int)fr * a.W + (int)fc)];
+        }
+#pragma unroll
+        for (int b = 0; b < kTsdfBatch; b++) {
+            if (wd[b] != wd[b]) continue;  // NaN: no update
+            const float t = (wd[b] - qw[b]) * a.inv_tau;
+            if (t >= -1.0f) {
+                s = s + (t < 1.0f ? t : 1.0f);
+                c = c + 1;
+            }
+        }
+    }
+    sum[node] = s;
+    count[node] = c;
+}
+
+// F = sum / count where count >= min_obs, else 1; mask[node] = 1 when the cell with that low corner has all 8 corners observed enough
+__global__ __launch_bounds__(256) void tsdf_field_kernel(int G, const float *__restrict__ sum, const int *__restrict__ count, int min_obs,
+                                                         float *__restrict__ F, unsigned char *__restrict__ mask)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t N3 = (size_t)G * G * G;
+    if (q >= N3) return;
+    const int i = (int)(q % G), j = (int)((q / G) % G), k = (int)(q / ((size_t)G * G));
+    const int c = count[q];
+    F[q] = c >= min_obs ? sum[q] / (float)c : 1.0f;
+    unsigned char m = 0;
+    if (i < G - 1 && j < G - 1 && k < G - 1) {
+        m = 1;
+#pragma unroll
+        for (int d = 0; d < 8; d++)
+            if (count[q + (size_t)(d & 1) + (size_t)((d >> 1) & 1) * G + (size_t)(d >> 2) * G * G] < min_obs) m = 0;
+    }
+    mask[q] = m;
+}
+
+}  // namespace
+
+}  // namespace mvs
+
+using namespace mvs;
+
+extern "C" {
+
+int mvs_tsdf_volume(mvs_ctx *ctx, int nodes_per_axis, const float origin3[3], float node_spacing, float truncation)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_volume: null context");
+    if (!origin3) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: origin is null");
+    const int G = nodes_per_axis;
+    if (G < kTsdfMinG || G > kTsdfMaxG) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: nodes_per_axis %d out of range %d..%d", G, kTsdfMinG, kTsdfMaxG);
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(origin3[c])) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: origin is not finite");
+    if (!(node_spacing > 0.f && node_spacing < INFINITY) || !(truncation > 0.f && truncation < INFINITY))
+        return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: node_spacing %g and truncation %g must be finite and > 0", node_spacing, truncation);
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N3 = (size_t)G * G * G;
+    ctx->tsdf_G = 0;  // no volume until the new one is allocated and cleared
+    int rc;
+    if ((rc = ensure(ctx, ctx->tsdf_vol, 8 * N3))) return rc;
+    MVS_HIP(ctx, hipMemsetAsync(ctx->tsdf_vol.ptr, 0, 8 * N3, ctx->stream));
+    ctx->tsdf_G = G;
+    for (int c = 0; c < 3; c++) ctx->tsdf_origin[c] = origin3[c];
+    ctx->tsdf_h = node_spacing;
+    ctx->tsdf_inv_tau = 1.0f / truncation;  // rounded once (contract step 4)
+    return MVS_OK;
+}
+
+int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cost)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_integrate: null context");
+    if (!slots) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: slots is null");
+    if (nslots < 1) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: nslots %d < 1", nslots);
+    if (!(max_cost >= 0.f)) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: max_cost %g must be >= 0", max_cost);
+    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "mvs_tsdf_integrate: no volume (mvs_tsdf_volume first)");
+    const int cap = (int)ctx->dstore.size();
+    for (int e = 0; e < nslots; e++)
+        if (slots[e] < 0 || slots[e] >= cap) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: slot %d outside the depth store (capacity %d)", slots[e], cap);
+    const bool use_cost = max_cost < INFINITY;
+    for (int e = 0; e < nslots; e++) {
+        const mvs_ctx::DepthSlot &s = ctx->dstore[slots[e]];
+        if (!s.have) return fail(ctx, MVS_ESTATE, "mvs_tsdf_integrate: slot %d holds no depth map (mvs_depth_upload)", slots[e]);
+        if (use_cost && !s.have_cost) return fail(ctx, MVS_ESTATE, "mvs_tsdf_integrate: max_cost %g is finite but slot %d was stored without a cost map", max_cost, slots[e]);
+    }
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const int W = ctx->W, H = ctx->H, G = ctx->tsdf_G;
+    const size_t P = (size_t)W * H, N3 = (size_t)G * G * G;
+    int rc;
+    if ((rc = ensure(ctx, ctx->tsdf_wmaps, (size_t)(nslots < kTsdfChunk ? nslots : kTsdfChunk) * P * sizeof(float)))) return rc;
+    float *wmaps = (float *)ctx->tsdf_wmaps.ptr;
+    float *sum = (float *)ctx->tsdf_vol.ptr;
+    int *count = (int *)(sum + N3);
+    WmapArgs wa;
+    IntegrateArgs ia;
+    memset(&wa, 0, sizeof(wa));
+    memset(&ia, 0, sizeof(ia));
+    wa.wmap = wmaps;
+    wa.W = W;
+    wa.H = H;
+    wa.use_cost = use_cost ? 1 : 0;
+    wa.invW = 1.0f / (float)W;
+    wa.invH = 1.0f / (float)H;
+    wa.max_cost = max_cost;
+    ia.wmap = wmaps;
+    ia.W = W;
+    ia.H = H;
+    ia.G = G;
+    ia.ox = ctx->tsdf_origin[0];
+    ia.oy = ctx->tsdf_origin[1];
+    ia.oz = ctx->tsdf_origin[2];
+    ia.h = ctx->tsdf_h;
+    ia.halfW = (float)W * 0.5f;
+    ia.halfH = (float)H * 0.5f;
+    ia.inv_tau = ctx->tsdf_inv_tau;
+    const dim3 igrid((unsigned)div_up(G, kTsdfTX), (unsigned)div_up(G, kTsdfTY), (unsigned)G);
+    ProfileScope ps(ctx, MVS_K_TSDF);
+    for (int e0 = 0; e0 < nslots; e0 += kTsdfChunk) {
+        const int n = nslots - e0 < kTsdfChunk ? nslots - e0 : kTsdfChunk;
+        for (int e = 0; e < n; e++) {
+            const int slot = slots[e0 + e];
+            const mvs_ctx::DepthSlot &s = ctx->dstore[slot];
+            wa.depth[e] = (const float *)ctx->dstore_depth.ptr + P * slot;
+            wa.cost[e] = use_cost ? (const float *)ctx->dstore_cost.ptr + P * slot : nullptr;
+            memcpy(wa.Pw[e], s.P + 12, 4 * sizeof(float));
+            memcpy(wa.Pi[e], s.Pi, sizeof(s.Pi));
+            memcpy(ia.P[e], s.P, 8 * sizeof(float));           // rows x, y
+            memcpy(ia.P[e] + 8, s.P + 12, 4 * sizeof(float));  // row w
+        }
+        ia.n = n;
+        tsdf_wmap_kernel<<<dim3((unsigned)div_up((int)P, 256), (unsigned)n), 256, 0, ctx->stream>>>(wa);
+        MVS_HIP(ctx, hipGetLastError());
+        tsdf_integrate_kernel<<<igrid, kTsdfTX * kTsdfTY, 0, ctx->stream>>>(ia, sum, count);
+        MVS_HIP(ctx, hipGetLastError());
+    }
+    return MVS_OK;
+}
+
+int mvs_tsdf_fetch(mvs_ctx *ctx, float *sdf_sum, int32_t *count)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_fetch: null context");
+    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "mvs_tsdf_fetch: no volume (mvs_tsdf_volume first)");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N3 = (size_t)ctx->tsdf_G * ctx->tsdf_G * ctx->tsdf_G;
+    const float *sum = (const float *)ctx->tsdf_vol.ptr;
+    if (sdf_sum) MVS_HIP(ctx, hipMemcpyAsync(sdf_sum, sum, N3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (count) MVS_HIP(ctx, hipMemcpyAsync(count, sum + N3, N3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MVS_OK;
+}
+
+int mvs_tsdf_surface(mvs_ctx *ctx, int min_observations, mvs_surface **out)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_surface: null context");
+    if (!out) return fail(ctx, MVS_EINVAL, "mvs_tsdf_surface: out is null");
+    *out = nullptr;
+    if (min_observations < 1) return fail(ctx, MVS_EINVAL, "mvs_tsdf_surface: min_observations %d < 1", min_observations);
+    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "mvs_tsdf_surface: no volume (mvs_tsdf_volume first)");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const int G = ctx->tsdf_G;
+    const size_t N3 = (size_t)G * G * G;
+    int rc;
+    if ((rc = ensure(ctx, ctx->tsdf_work, 5 * N3))) return rc;
+    const float *sum = (const float *)ctx->tsdf_vol.ptr;
+    float *F = (float *)ctx->tsdf_work.ptr;
+    unsigned char *mask = (unsigned char *)(F + N3);
+    tsdf_field_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, ctx->stream>>>(G, sum, (const int *)(sum + N3), min_observations, F, mask);
+    MVS_HIP(ctx, hipGetLastError());
+    mvs_surface *res = new (std::nothrow) mvs_surface;
+    if (!res) return fail(ctx, MVS_ENOMEM, "mvs_tsdf_surface: host allocation failed");
+    res->grid.G = G;
+    res->grid.ox = ctx->tsdf_origin[0];
+    res->grid.oy = ctx->tsdf_origin[1];
+    res->grid.oz = ctx->tsdf_origin[2];
+    res->grid.h = ctx->tsdf_h;
+    res->iso = 0.0f;
+    res->spacing = ctx->tsdf_h;
+    res->ratio_kept = 1;
+    res->support_cells = 0;
+    std::string why;
+    const int mrc = surface_nets_device(res->grid, F, 0.0f, mask, ctx->stream, res, "mvs_tsdf_surface", why);
+    if (mrc != MVS_OK) {
+        delete res;
+        return fail(ctx, mrc, "%s", why.c_str());
+    }
+    *out = res;
+    return MVS_OK;
+}
+
+}  // extern "C"

@@ -25,7 +25,7 @@ MVS_SHARD_ROWS, MVS_SHARD_VIEWS, MVS_SHARD_VIEWS_SCATTER = 0, 1, 2
 SHARD_MODES = {"rows": 0, "views": 1, "views_scatter": 2}
 MVS_SAMPLER_FIXED, MVS_SAMPLER_EXACT_F32 = 0, 1
 SAMPLERS = {"fixed": MVS_SAMPLER_FIXED, "exact": MVS_SAMPLER_EXACT_F32}
-MVS_K_SWEEP, MVS_K_ARGMIN, MVS_K_PLAN, MVS_K_RASTER, MVS_K_PROJECT, MVS_K_FLOW, MVS_K_FUSE = 0, 1, 2, 3, 4, 5, 6
+MVS_K_SWEEP, MVS_K_ARGMIN, MVS_K_PLAN, MVS_K_RASTER, MVS_K_PROJECT, MVS_K_FLOW, MVS_K_FUSE, MVS_K_TSDF = 0, 1, 2, 3, 4, 5, 6, 7
 MVS_K_COUNT = 8
 BACKGROUND_DEPTH = np.float32(1.0)
 
@@ -86,6 +86,10 @@ ABI = [
     ("mvs_fuse_depth", _i, [_vp, _i, _i, _i32p, _i, _f, _f, _f, _fp, C.POINTER(_i)]),
     ("mvs_fuse_points_device", _vp, [_vp]),
     ("mvs_depth_slot_matrices", _i, [_vp, _i, _fp]),
+    ("mvs_tsdf_volume", _i, [_vp, _i, _fp, _f, _f]),
+    ("mvs_tsdf_integrate", _i, [_vp, _i, _i32p, _f]),
+    ("mvs_tsdf_fetch", _i, [_vp, _fp, _i32p]),
+    ("mvs_tsdf_surface", _i, [_vp, _i, _vp]),
     ("mvs_sweep_argmin", _i, [_vp]),
     ("mvs_sweep_refine_depth", _i, [_vp]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
@@ -750,6 +754,49 @@ class Context:
         m = np.empty(36, np.float32)
         self._check(self.lib.mvs_depth_slot_matrices(self.h, int(slot), _ptr(m, _fp)))
         return m[:16].reshape(4, 4).copy(), m[16:32].reshape(4, 4).copy(), m[32:].copy()
+
+    # ---- TSDF fusion -------------------------------------------------------------------------------
+    def tsdf_volume(self, nodes_per_axis, origin, node_spacing, truncation):
+        """mvs_tsdf_volume: a cleared G^3 volume, node (i, j, k) at origin + node_spacing (i, j, k); again: cleared"""
+        o = _f32(origin, (3,))
+        self._check(self.lib.mvs_tsdf_volume(self.h, int(nodes_per_axis), _ptr(o, _fp), float(node_spacing), float(truncation)))
+        self._tsdf_G = int(nodes_per_axis)
+
+    def tsdf_integrate(self, slots, max_cost=float("inf")):
+        """mvs_tsdf_integrate: add the listed depth-store slots' maps, in list order (asynchronous, stream-ordered)"""
+        sl = np.ascontiguousarray(np.asarray(list(slots) if len(slots) else [0], dtype=np.int32))
+        self._check(self.lib.mvs_tsdf_integrate(self.h, len(slots), _ptr(sl, _i32p), float(max_cost)))
+
+    def tsdf_fetch(self):
+        """mvs_tsdf_fetch -> (sum [G, G, G] f32, count [G, G, G] i32), indexed [k][j][i]"""
+        G = getattr(self, "_tsdf_G", 0)
+        if not G:   # no volume made through this object: the library's answer (MVS_ESTATE before mvs_tsdf_volume)
+            self._check(self.lib.mvs_tsdf_fetch(self.h, None, None))
+            raise MvsError("tsdf_fetch: the volume was not made with tsdf_volume")
+        s = np.empty((G, G, G), np.float32)
+        c = np.empty((G, G, G), np.int32)
+        try:
+            self._check(self.lib.mvs_tsdf_fetch(self.h, _ptr(s, _fp), _ptr(c, _i32p)))
+        finally:
+            self._depth_keep = {}
+        return s, c
+
+    def tsdf_surface(self, min_observations=1):
+        """mvs_tsdf_surface -> (vertices N x 4 f32 with w = 1, faces F x 3 i32 facing the cameras); the surface is freed here"""
+        s = C.c_void_p()
+        try:
+            self._check(self.lib.mvs_tsdf_surface(self.h, int(min_observations), C.byref(s)))
+        finally:
+            self._depth_keep = {}
+        try:
+            nv, nf = C.c_int(), C.c_int()
+            self.lib.mvs_surface_counts(s, C.byref(nv), C.byref(nf))
+            v = np.zeros((nv.value, 4), np.float32)
+            f = np.zeros((nf.value, 3), np.int32)
+            self.lib.mvs_surface_fetch(s, v.ctypes.data_as(_vp), f.ctypes.data_as(_vp))
+        finally:
+            self.lib.mvs_surface_free(s)
+        return v, f
 
     def depth_device_array(self):
         """zero-copy [H, W] f32 view of the device depth map for torch.as_tensor(..., device='cuda') (valid until the
