@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <array>
 #include <vector>
 
 #include "../../include/mvs.h"
@@ -92,6 +93,7 @@ struct mvs_ctx {
     int rect_rs = 0, rect_slot_dw = 0, rect_dpad = 0;
     std::vector<unsigned char> rect_cold_host;  // host copy of the kernel's cold block (sweep_rect.hip: RectCold)
     bool rect_cold_sent = false;
+    std::array<int, 5> rect_order{};  // the region order the X / Y records are packed for: view range, chunk range, chunks per workgroup (sweep_rect.hip: RectOrder)
     hipEvent_t plan_event = nullptr;  // the rectified planner's read-back has landed (the host waits for this, not for the whole stream)
     mvs::DevBuf probe_buf;           // mvs_depth_probe: pixel coordinates in, depths out
     mvs::DevBuf raster_bins;         // face binning of large meshes: per-bin counts / offsets / lists, shared list of large faces

@@ -26,8 +26,12 @@
 // Region pipeline.  Per (chunk, view) the planner's box of the view's quad image is copied into one of two LDS slots by
 // buffer_load_dwordx4 ... lds (dense rows of RS quads, 1 KiB = 64 lanes x 16 B per instruction, per-lane source offsets fixed for the
 // launch), one region ahead of the one being sampled; s_waitcnt vmcnt(0) + one s_barrier per region make every wavefront's part
-// visible and free the slot the next copy goes to.  The X / Y records of the coming regions travel through vector registers (lane l =
-// dword l, v_readlane when the region's turn comes).  A region's sampling is inline asm in two shapes, chosen by one wave-uniform test
+// visible and free the slot the next copy goes to.  The copies carry no lane mask: they go through a buffer resource that ends with
+// the box's last row, and the range check drops the lanes past it.  The X / Y records lie in the order a workgroup takes its regions
+// (the next region's records are the next 256 bytes), travel through vector registers one region ahead (lane l = dword l), are added
+// lane by lane when the region's turn comes, and every scalar of the turn -- the four LDS offsets, the four weight words, the clean
+// test, the source and the end of the NEXT region's copy -- is one v_readlane of the sum with no arithmetic behind it
+// (plan_rect_pack).  A region's sampling is inline asm in two shapes, chosen by one wave-uniform test
 // per region: CLEAN (all four planes FULL) is one straight-line statement for the four planes, the next plane's reads in flight behind
 // the current plane's arithmetic; otherwise one statement per plane (M0-based ds_read_addtid_b32, v_dot4_u32_u8, v_sad_u16; border
 // planes under EXEC masks, planes with nothing in frame branched over) plus the block for failed certificates.  Not compiler code: the
@@ -40,6 +44,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <array>
 #include <type_traits>
 #include <vector>
 
@@ -85,28 +90,6 @@ __device__ __forceinline__ void wait_vm()
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// wait until at most n of this wavefront's vector-memory operations are outstanding (n wave-uniform)
-__device__ __forceinline__ void wait_vmcnt(int n)
-{
-    // a smaller count than asked for is always safe (it waits for more)
-    switch (n) {
-    case 1: wait_vm<1>(); break;
-    case 2: wait_vm<2>(); break;
-    case 3: wait_vm<3>(); break;
-    case 4: wait_vm<4>(); break;
-    case 5: wait_vm<5>(); break;
-    case 6: wait_vm<6>(); break;
-    case 7: wait_vm<6>(); break;
-    case 8: wait_vm<8>(); break;
-    case 9: wait_vm<9>(); break;
-    case 10: case 11: wait_vm<10>(); break;
-    case 12: case 13: case 14: wait_vm<12>(); break;
-    case 15: case 16: case 17: wait_vm<15>(); break;
-    case 18: wait_vm<18>(); break;
-    default: wait_vm<0>(); break;
-    }
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------
@@ -141,8 +124,8 @@ struct RectTables {
     uint32_t *xt, *yt;    // [T][V][dpad]   full entries (below)
     uint32_t *xmm, *ymm;  // [T][V][dpad]   lowest | highest << 16 integer texel over the tile's in-frame pixels, 0xffffffff if none
     uint32_t *wt;         // [V][dpad]      weight word of the view's nominal phase pair at that plane
-    uint32_t *xw;         // [tiles_x][V][NC][4 wavefronts][8]  X records (pass C)
-    uint32_t *yr;         // [tiles_y][V][NC][4 wavefronts][4]  Y records
+    uint32_t *xw;         // [tiles_x][NC][views of the launch][4 wavefronts][16]  X records (pass C)
+    uint32_t *yr;         // [tiles_y][NC][views of the launch][4 wavefronts][16]  Y records
     uint32_t *xbox, *ybox;  // [T][V][NC]   region boxes (pass B)
     int *stats;           // [0] widest region (quads), [1] tallest region (rows), [2] planes that are not FULL (diagnostic)
     int dpad;
@@ -250,19 +233,45 @@ __global__ __launch_bounds__(256) void plan_rect_box(SweepParams p, RectTables r
     if (live) (which == 0 ? rt.xbox : rt.ybox)[tid] = org | (min(ext, 0x7fffu) << 16) | (any ? 1u << 31 : 0u);
 }
 
-// Pass C (after the host has chosen the row stride RS of the LDS slots from pass B's counters).  One thread per (tile column or
-// tile row, view, chunk, wavefront): that wavefront's record of the region.  Per plane a 16-bit field with the plane's share of the
-// LDS byte offset of the texel quad of the tile's pixel 0 -- x: 4 (ix - x0 + RX_BIAS_X); y: 4 RS (iy - y0 + RX_BIAS_Y); the biases
-// because pixel 0 of a tile that is partly out of frame lies left of / above the box (the kernel's copies land RX_BIAS bytes into
-// the slot, so base + x share + y share is the quad's address; the sum stays below 2^14) -- or a flag (x: bit 14, y: bit 15) = the
-// certificate failed, look at the full entry.  A plane whose certificate holds but whose tile is partly (MASKED) or wholly (NONE) out
-// of frame has no flag: its out-of-frame pixels come as a mask byte per plane (x: n | side << 7 as in the full entry, n = 64: nothing
-// in frame; y: the bit mask of the rows that are OUT of frame), zero for FULL planes.
-//   X record (8 dwords): x01, x23, W0, W1, W2, W3, 4 x0 | (any ? RS / 4 : 0) << 16, x masks of the four planes
-//   Y record (8 dwords): y01, y23, 4 (pad_slab v + y0 pitch), (any ? rows : 0) | y0 << 8, y masks of the four planes, 0, 0, 0
+// Pass C (after the host has chosen the row stride RS of the LDS slots from pass B's counters, and again whenever a launch walks the
+// regions in another order).  One thread per (tile column or tile row, view, chunk, wavefront): that wavefront's record of the region,
+// 16 dwords.  The sweep kernel adds the X record of its tile column and the Y record of its tile row LANE BY LANE (one v_add_u32) and
+// takes every scalar of a region's turn from the sum with one v_readlane and nothing behind it -- so each dword is either one table's
+// alone (the other holds 0 there) or a sum that means something:
+//   dword   X record                                      Y record
+//   0 - 3   plane k: 4 (ix - x0 + RX_BIAS_X), or bit 14   plane k: 4 RS (iy - y0 + RX_BIAS_Y), or bit 15
+//   4       NEXT region: 4 x0                             NEXT region: byte offset of its first row in the quad images
+//   5       NEXT region: 4 x0                             NEXT region: that + the bytes its copy spans (below)
+//           (a table whose box of the NEXT region is empty: dword 4 = RX_NO_COPY resp. 0, dword 5 = 0 -- the sum ends the copy before its start)
+//   6 - 9   weight word of plane k                        0
+//   10      1 if any field has the flag or any mask byte is not 0 (both tables: the sum is 0 for a CLEAN region)
+//   11      x masks of the four planes                    0
+//   12      0                                             y masks of the four planes
+//   13      4 x0 | (any ? RS / 4 : 0) << 16               0
+//   14      0                                             (any ? rows : 0) | y0 << 8
+//   15      0                                             byte offset of THIS region's first row (the workgroup's first copy)
+// Plane fields: the plane's share of the LDS byte offset of the texel quad of the tile's pixel 0; the biases because pixel 0 of a tile
+// that is partly out of frame lies left of / above the box (the kernel's copies land RX_BIAS bytes into the slot, so base + x share +
+// y share is the quad's address; the sum stays below 2^14) -- or a flag (x: bit 14, y: bit 15) = the certificate failed, look at the
+// full entry.  A plane whose certificate holds but whose tile is partly (MASKED) or wholly (NONE) out of frame has no flag: its
+// out-of-frame pixels come as a mask byte per plane (x: n | side << 7 as in the full entry, n = 64: nothing in frame; y: the bit mask
+// of the rows that are OUT of frame), zero for FULL planes.
+// NEXT region: a workgroup takes its regions chunks outer, views inner, so the records are laid out in that order
+// ([tile][chunk][view of the launch][wavefront], "the next region" = the next 256 bytes) and each carries what the copy of its
+// successor needs: the copy is issued a region ahead.  Bytes the copy spans: the kernel's copy instructions have per-lane source
+// offsets that grow with the 16-byte unit's index in the box (row-major, RS quads per row), so a buffer that ends
+// "4 ((rows - 1) pitch + RS)" bytes behind the box's first quad makes the hardware's range check drop exactly the units past the
+// box's last row: no lane mask, no branch.  A workgroup's last region has no NEXT one (RectOrder: the launch's view range, chunk
+// range and chunks per workgroup): both tables write it as an empty box.
 constexpr int RX_BIAS_X = 64, RX_BIAS_Y = 8;  // quads / rows
+constexpr uint32_t RX_NO_COPY = 1u << 24;     // more than any copy spans (32 rows of a 16383-pixel image: 2.1 MB)
+constexpr int RX_REC = 16;                    // dwords per record
 
-__global__ __launch_bounds__(256) void plan_rect_pack(SweepParams p, RectTables rt, int RS)
+struct RectOrder {
+    int v0, vcount, chunk0, chunk1, cps;
+};
+
+__global__ __launch_bounds__(256) void plan_rect_pack(SweepParams p, RectTables rt, int RS, RectOrder o, int count_stats)
 {
     const int NC = p.nchunks, dpad = rt.dpad;
     const int nx = p.tiles_x * p.V * NC * 4, ny = p.tiles_y * p.V * NC * 4;
@@ -272,12 +281,14 @@ __global__ __launch_bounds__(256) void plan_rect_pack(SweepParams p, RectTables 
     if (which == 1) tid -= nx;
     const int w = tid & 3, chunk = (tid >> 2) % NC, v = ((tid >> 2) / NC) % p.V, t = (tid >> 2) / (NC * p.V);
     const uint32_t *ent = (which == 0 ? rt.xt : rt.yt) + ((size_t)t * p.V + v) * dpad + chunk * RX_PC + w * RX_KW;
-    const uint32_t box = (which == 0 ? rt.xbox : rt.ybox)[tid >> 2];
+    const uint32_t *boxes = which == 0 ? rt.xbox : rt.ybox;
+    const uint32_t box = boxes[tid >> 2];
     const int org = (int)(box & 0xffffu), ext = (int)((box >> 16) & 0x7fffu);
     const bool any = (box >> 31) != 0u;
     const int size = which == 0 ? TILE_W : RX_TILE_H;
     uint32_t f[RX_KW], masks = 0u;
     int not_full = 0;
+    bool flagged = false;
     for (int k = 0; k < RX_KW; k++) {
         const uint32_t e = ent[k];
         const int tex = ((int)(e & 0xfffffu) - RX_BIAS) >> 5;
@@ -289,6 +300,7 @@ __global__ __launch_bounds__(256) void plan_rect_pack(SweepParams p, RectTables 
         const bool certified = (e & RX_UNIFORM) != 0u && (nothing || (rel >= 0 && rel < ext + 2 * bias));
         if (!certified) {
             f[k] = which == 0 ? 0x4000u : 0x8000u;
+            flagged = true;
         } else {
             f[k] = nothing ? 0u : (uint32_t)rel * (which == 0 ? 4u : 4u * (uint32_t)RS);
             uint32_t m;
@@ -300,30 +312,46 @@ __global__ __launch_bounds__(256) void plan_rect_pack(SweepParams p, RectTables 
         }
         not_full += (!certified || ((masks >> (8 * k)) & 0xffu)) ? 1 : 0;
     }
-    {
+    if (count_stats) {
         const int n = wave_sum_i32(live ? not_full : 0);
         if ((threadIdx.x & 63) == 0 && n) atomicAdd(rt.stats + 2, n);
     }
-    if (!live) return;
+    const int vend = o.v0 + o.vcount;
+    if (!live || v < o.v0 || v >= vend) return;
+    // the region the workgroup turns to after this one; none after the last region of its share
+    const bool last_view = v + 1 == vend;
+    const int vn = last_view ? o.v0 : v + 1, cn = last_view ? chunk + 1 : chunk;
+    const bool ends = last_view && (chunk < o.chunk0 || chunk + 1 >= o.chunk1 || (chunk + 1 - o.chunk0) % o.cps == 0);
+    const uint32_t nbox = ends || cn >= NC ? 0u : boxes[((size_t)t * p.V + vn) * NC + cn];
+    const uint32_t norg = nbox & 0xffffu, next = (nbox >> 16) & 0x7fffu;
+    const bool nany = (nbox >> 31) != 0u;
+    auto first_row = [&](int view, uint32_t y0) {  // (frame-store slot: mvs_sweep_handles)
+        return 4u * ((uint32_t)p.pad_slab * (uint32_t)(p.view_slot ? p.view_slot[view] : view) + y0 * (uint32_t)p.pitch);
+    };
+    const uint32_t clean = (flagged || masks) ? 1u : 0u;
+    const size_t slot = (((size_t)t * NC + chunk) * o.vcount + (v - o.v0)) * 4 + w;
+    uint32_t *rec = (which == 0 ? rt.xw : rt.yr) + slot * RX_REC;
+    for (int k = 0; k < RX_KW; k++) rec[k] = f[k];
     if (which == 0) {
-        uint32_t *rec = rt.xw + (size_t)tid * 8;
         const uint32_t *wv = rt.wt + (size_t)v * dpad + chunk * RX_PC + w * RX_KW;
-        rec[0] = f[0] | (f[1] << 16);
-        rec[1] = f[2] | (f[3] << 16);
-        rec[2] = wv[0];
-        rec[3] = wv[1];
-        rec[4] = wv[2];
-        rec[5] = wv[3];
-        rec[6] = 4u * (uint32_t)org | ((any ? (uint32_t)RS / 4u : 0u) << 16);
-        rec[7] = masks;
+        rec[4] = nany ? 4u * norg : RX_NO_COPY;
+        rec[5] = nany ? 4u * norg : 0u;
+        for (int k = 0; k < RX_KW; k++) rec[6 + k] = wv[k];
+        rec[10] = clean;
+        rec[11] = masks;
+        rec[12] = 0u;
+        rec[13] = 4u * (uint32_t)org | ((any ? (uint32_t)RS / 4u : 0u) << 16);
+        rec[14] = rec[15] = 0u;
     } else {
-        uint32_t *rec = rt.yr + (size_t)tid * 8;
-        rec[0] = f[0] | (f[1] << 16);
-        rec[1] = f[2] | (f[3] << 16);
-        rec[2] = 4u * ((uint32_t)p.pad_slab * (uint32_t)(p.view_slot ? p.view_slot[v] : v) + (uint32_t)(org * p.pitch));  // (frame-store slot: mvs_sweep_handles)
-        rec[3] = (any ? (uint32_t)ext : 0u) | ((uint32_t)org << 8);
-        rec[4] = masks;
-        rec[5] = rec[6] = rec[7] = 0u;
+        rec[4] = nany ? first_row(vn, norg) : 0u;
+        rec[5] = nany ? rec[4] + 4u * ((next - 1u) * (uint32_t)p.pitch + (uint32_t)RS) : 0u;
+        rec[6] = rec[7] = rec[8] = rec[9] = 0u;
+        rec[10] = clean;
+        rec[11] = 0u;
+        rec[12] = masks;
+        rec[13] = 0u;
+        rec[14] = (any ? (uint32_t)ext : 0u) | ((uint32_t)org << 8);
+        rec[15] = first_row(v, (uint32_t)org);
     }
 }
 
@@ -340,7 +368,7 @@ struct RectCold {
     float *depth, *cost;
     int *index;
     float invW, invH;
-    int dpad, pad_;
+    int dpad, v0;  // (v0: the launch's first view -- RectArgs has it too; the failed-certificate block reads it here)
 };
 
 struct RectArgs {
@@ -388,6 +416,16 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
     const bool col_ok = col < a.W;
     const int NC = a.nchunks;
 
+    // per-lane source offsets (bytes) of this wavefront's copy instructions: instruction i = wave + 4 t fills LDS dwords
+    // [256 i, 256 i + 256) of the slot = 16-byte units g = 64 i + lane of the dense [row][RS] region image.  They grow with g
+    // (pitch >= RS), so the units of a region's box are exactly those whose offset lies below the size plan_rect_pack put into the
+    // region's record: the copies run through a buffer resource of that size and the range check drops the rest.
+    uint32_t srcoff[RX_MAX_NI];
+#pragma unroll
+    for (int t = 0; t < RX_MAX_NI; t++) {
+        const int g = (wave + 4 * t) * 64 + lane;
+        srcoff[t] = 4u * (uint32_t)((g / UNITS) * a.pitch + (g % UNITS) * 4);
+    }
     uint32_t Im255[8];
     {
         const uint8_t *img = RX_COLD(a.cold, const uint8_t *, main_img);
@@ -395,84 +433,45 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
         for (int j = 0; j < 8; j++) Im255[j] = (col_ok && row0 + j < a.H) ? 255u * (uint32_t)img[(size_t)(row0 + j) * a.W + col] : 0u;
     }
 
-    // per-lane source offsets (bytes) of this wavefront's copy instructions: instruction i = wave + 4 t fills LDS dwords
-    // [256 i, 256 i + 256) of the slot = 16-byte units g = 64 i + lane of the dense [row][RS] region image
-    uint32_t srcoff[RX_MAX_NI];
-#pragma unroll
-    for (int t = 0; t < RX_MAX_NI; t++) {
-        const int g = (wave + 4 * t) * 64 + lane;
-        srcoff[t] = 4u * (uint32_t)((g / UNITS) * a.pitch + (g % UNITS) * 4);
-    }
+    // copy instructions of this wavefront per region: a constant of the launch (the slot holds a.slot_dw / 256 instructions' worth;
+    // one more would land in the other slot)
+    const int ni_wave = (a.slot_dw / 256 + 3 - wave) >> 2;
 
     const int chunk_first = a.chunk0 + (int)blockIdx.y * a.cps;
     const int chunk_last = min(a.chunk1, chunk_first + a.cps);
-    const int vend = a.v0 + a.vcount;
     const int nreg = (chunk_last - chunk_first) * a.vcount;
 
-    // this wavefront's records of region (chunk, v), e = v NC + chunk: 8 dwords at xw_wg + 128 e bytes, 8 dwords at yr_wg + 128 e bytes;
-    // both tables live in one allocation (a.xw < a.yr): one resource, two wave-uniform offsets
+    // this wavefront's records of the workgroup's regions, in the order it takes them (plan_rect_pack): 16 dwords every 256 bytes from
+    // `xo` (tile column) and from `xo + ydelta` (tile row); both tables live in one allocation (a.xw < a.yr): one resource, two offsets
     const __amdgpu_buffer_rsrc_t rtab = make_rsrc(a.xw, 0xffffffffu);
-    const uint32_t xw_wg = (uint32_t)(((size_t)tx * a.V * NC * 4 + wave) * 32);
-    const uint32_t yr_wg = (uint32_t)((size_t)((const char *)a.yr - (const char *)a.xw) + ((size_t)ty * a.V * NC * 4 + wave) * 32);
-    const __amdgpu_buffer_rsrc_t rquads = make_rsrc(a.quads, 0xffffffffu);
+    uint32_t xo = (uint32_t)(((((size_t)tx * NC + chunk_first) * a.vcount) * 4 + wave) * (4 * RX_REC));
+    const uint32_t ydelta = (uint32_t)((size_t)((const char *)a.yr - (const char *)a.xw) + ((((size_t)ty * NC + chunk_first) * a.vcount) * 4 + wave) * (4 * RX_REC)) - xo;
 
-    // request a region into the slot at LDS dword `slot_dw0`: xsx = X record dword 6 (4 x0 | units per row << 16, 0 units if the box is
-    // empty), ysrc / yn = Y record dwords 2 / 3 (byte offset of the box's first row in the quad images; rows | y0 << 8).  Rows of RS
-    // quads, 64 16-byte units per instruction; only the last instruction of a region runs under a lane mask.
-    auto issue_copy = [&](uint32_t xsx, uint32_t ysrc, uint32_t yn, uint32_t slot_dw0) {
-        const int n = (int)((yn & 0xffu) * (xsx >> 16));
-        const uint32_t src = (xsx & 0xffffu) + ysrc;
-        uint32_t *dst = smem + slot_dw0 + SLOT_BIAS_DW + wave * 256;  // (the records' offsets are biased: pixel 0 of a partly visible tile lies before the box)
-        const int left = n - wave * 64;  // units of the region this wavefront still has to copy (wave-uniform)
-        auto copy = [&](int t, bool whole) {
-            int lim = left - 256 * t;
-            asm volatile("" : "+s"(lim));  // (or the compiler folds the uniform test that led here into this per-lane one: an EXEC mask and its branch per instruction)
-            if (whole || lane < lim)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rquads, (__attribute__((address_space(3))) void *)(dst + t * 1024), 16, srcoff[t], src, 0, 0);
-        };
-        // whole instructions, then the region's last one under a lane mask; nothing left: no later instruction of this wavefront either
-        static_assert(RX_MAX_NI == 3, "the nest below");
-        if (left >= 64) {
-            copy(0, true);
-            if (left >= 320) {
-                copy(1, true);
-                if (left >= 576)
-                    copy(2, true);
-                else if (left > 512)
-                    copy(2, false);
-            } else if (left > 256) {
-                copy(1, false);
-            }
-        } else if (left > 0) {
-            copy(0, false);
-        }
+    // request a region into the slot at LDS byte `slot_b`: src = byte offset of the box's first quad in the quad images (the copies'
+    // scalar offset), end = where the copy stops fetching, counted like src from the start of the quad images (the size of the buffer
+    // resource the copies go through: gfx950 drops a lane whose offset PLUS the scalar offset reaches it; end <= src: nothing is
+    // fetched).  Every wavefront issues all its instructions for every region, whole wavefront, no EXEC write: a lane past the box's
+    // last row fetches nothing (the slot has room for it: a.slot_dw counts whole instructions, and no read goes there).
+    typedef __attribute__((address_space(3))) char *lds_ptr;
+    const uint32_t wdst = lds_base + 4u * (uint32_t)(SLOT_BIAS_DW + wave * 256);
+    auto issue_copy = [&](uint32_t src, uint32_t end, uint32_t slot_b) {
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)a.quads, 0, (int)end, 0x00020000);
+        const lds_ptr dst = (lds_ptr)(uintptr_t)(wdst + slot_b);
+        static_assert(RX_MAX_NI == 3, "the three lines below");
+        int ni = ni_wave;
+        asm volatile("" : "+s"(ni));  // (compared where it is used, s_cmp + s_cbranch_scc: or the tests live in SGPR pairs over the whole loop)
+        if (ni >= 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst, 16, srcoff[0], src, 0, 0);
+        if (ni >= 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst + 4096, 16, srcoff[1], src, 0, 0);
+        if (ni >= 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst + 8192, 16, srcoff[2], src, 0, 0);
     };
 
-    // The records of the coming regions travel through VECTOR registers (lane l holds dword l of the record; one v_readlane each when
-    // the region's turn comes): as scalar loads they would have to stay in SGPRs across a whole region's sampling, and the compiler
-    // spills them right after the load (a wait for the load, then v_writelane / v_readlane pairs) -- measured: 0.65 ms of loop skeleton.
-    const uint32_t lane8 = 4u * (uint32_t)(lane & 7);
-    auto load_x = [&](uint32_t xo) { return __builtin_amdgcn_raw_buffer_load_b32(rtab, lane8, xo, 0); };
-    auto load_y = [&](uint32_t yo) { return __builtin_amdgcn_raw_buffer_load_b32(rtab, lane8, yo, 0); };
+    // The records travel through VECTOR registers (lane l holds dword l; one v_readlane per scalar when the region's turn comes): as
+    // scalar loads they would have to stay in SGPRs across a whole region's sampling, and the compiler spills them right after the
+    // load (a wait for the load, then v_writelane / v_readlane pairs) -- measured: 0.65 ms of loop skeleton.  One region ahead: the
+    // record of region r + 1 is in flight while region r is sampled; what the copy of region r + 1 needs is in the record of region r.
+    const uint32_t lane16 = 4u * (uint32_t)(lane & (RX_REC - 1));
+    auto load_rec = [&](uint32_t o) { return __builtin_amdgcn_raw_buffer_load_b32(rtab, lane16, o, 0); };
     auto rdl = [](uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); };
-    // Region order of this workgroup: chunks outer, views inner.  A cursor = (views left in the chunk, byte offsets of the region's
-    // X and Y records); past the workgroup's last region it stays there (prefetches re-read the last records).
-    struct Cursor {
-        int vleft, left;  // views left in this chunk after this one; regions left after this one
-        uint32_t xo;      // byte offset of the region's X record; the Y records are walked in step: Y record at xo + ydelta
-    };
-    const uint32_t xstep = 128u * (uint32_t)NC;  // next view, same chunk
-    const int vlast = a.vcount - 1;
-    const uint32_t xwrap = 128u - xstep * (uint32_t)vlast;  // first view of the next chunk
-    auto advance = [&](Cursor &c) {
-        if (c.left <= 0) return;
-        c.left--;
-        const bool wrap = c.vleft == 0;
-        c.xo += wrap ? xwrap : xstep;
-        c.vleft = wrap ? vlast : c.vleft - 1;
-    };
-    const uint32_t x_first = xw_wg + 128u * (uint32_t)(a.v0 * NC + chunk_first);
-    const uint32_t ydelta = yr_wg - xw_wg;
 
     uint32_t acc[8][RX_KW];
     uint32_t best[8];
@@ -487,43 +486,40 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
     bool plain = true;    // depth selection: every cell so far carries the same count (see the chunk epilogue)
     uint32_t spacc = 0u;  // per plane of this wavefront (one byte each): views of the current chunk whose plane was NOT counted as a whole
 
-    Cursor c2;  // region r + 2: the one whose records are fetched next
-    c2.vleft = vlast;
-    c2.left = nreg - 1;
-    c2.xo = x_first;
-    // prologue: the records of regions 0 and 1, the copy of region 0
-    uint32_t x0r = load_x(c2.xo), y0r = load_y(c2.xo + ydelta);  // region r
-    advance(c2);
-    uint32_t x1r = load_x(c2.xo), y1r = load_y(c2.xo + ydelta);  // region r + 1
-    advance(c2);
-    uint32_t slot_cur = 0u, slot_nxt = (uint32_t)a.slot_dw;  // LDS dword offsets of the two slots
-    if (nreg > 0) issue_copy(rdl(x0r, 6), rdl(y0r, 2), rdl(y0r, 3), slot_cur);
-    int chunk = chunk_first, v = a.v0;
+    // prologue: the record of region 0 and, from its own fields, the copy of region 0
+    uint32_t xl = load_rec(xo), yl = load_rec(xo + ydelta);
+    xo += 4u * 4u * RX_REC;
+    const uint32_t slot_bytes = 4u * (uint32_t)a.slot_dw;
+    uint32_t slot_cur = 0u;  // LDS byte offset of the slot being sampled: 0 or slot_bytes
+    asm volatile("" : "+s"(slot_cur));  // (a scalar from the start: sharing the accumulators' zero would take it, and every M0 after it, through vector registers)
+    if (nreg > 0) {
+        const uint32_t xsx = rdl(xl, 13), rows = (xsx >> 16) ? rdl(yl, 14) & 0xffu : 0u;
+        const uint32_t src = (xsx & 0xffffu) + rdl(yl, 15);
+        issue_copy(src, rows ? src + 4u * ((rows - 1u) * (uint32_t)a.pitch + (uint32_t)RS) : 0u, slot_cur);
+    }
+    int chunk = chunk_first, vleft = a.vcount;  // views of the chunk still to come, this one included
 
-    for (int r = 0; r < nreg; r++) {
+    for (int r = nreg; r > 0; r--) {
         // every copy and every record this wavefront asked for has landed ...
         wait_vm<0>();
         // ... and so have every other wavefront's; nobody reads region r - 1 any more
         __builtin_amdgcn_s_barrier();
-        // request region r + 1 into the other slot and the records of region r + 2: in flight during this region's sampling
-        if (r + 1 < nreg) issue_copy(rdl(x1r, 6), rdl(y1r, 2), rdl(y1r, 3), slot_nxt);
-        const uint32_t x2r = load_x(c2.xo), y2r = load_y(c2.xo + ydelta);
-        advance(c2);
-        const uint32_t rsum = x0r + y0r;                            // (one vector add, two v_readlane: not four and two scalar adds)
-        const uint32_t sum01 = rdl(rsum, 0), sum23 = rdl(rsum, 1);  // per plane: LDS byte offset, or a flag bit
-        const uint32_t we[RX_KW] = {rdl(x0r, 2), rdl(x0r, 3), rdl(x0r, 4), rdl(x0r, 5)};
-        const uint32_t fmask = 0xffffu;
-        const uint32_t fld[RX_KW] = {sum01 & fmask, (sum01 >> 16) & fmask, sum23 & fmask, (sum23 >> 16) & fmask};
+        // this region's scalars, lane by lane (plan_rect_pack): one vector add, then one v_readlane each
+        const uint32_t rsum = xl + yl;
+        // the record of region r + 1 and the copy of region r + 1 into the other slot (nothing behind a workgroup's last region: its
+        // record ends the copy where it starts): in flight during this region's sampling
+        xl = load_rec(xo);
+        yl = load_rec(xo + ydelta);
+        xo += 4u * 4u * RX_REC;
+        issue_copy(rdl(rsum, 4), rdl(rsum, 5), slot_cur ^ slot_bytes);
+        const uint32_t we[RX_KW] = {rdl(rsum, 6), rdl(rsum, 7), rdl(rsum, 8), rdl(rsum, 9)};
+        const uint32_t fld[RX_KW] = {rdl(rsum, 0), rdl(rsum, 1), rdl(rsum, 2), rdl(rsum, 3)};  // per plane: LDS byte offset, or a flag bit
 
         // ---- sample region r ----
-        const uint32_t special = (sum01 | sum23) & 0xc000c000u;
         {
-            const uint32_t slot_byte = lds_base + slot_cur * 4u;
+            const uint32_t slot_byte = lds_base + slot_cur;
             uint32_t qd[1][8];
-            // per plane: what is out of frame although the certificates hold (0: nothing -- with no flag in the field that is a FULL plane)
-            const uint32_t xmasks = rdl(x0r, 7), ymasks = rdl(y0r, 4);
-            const uint32_t anymask = xmasks | ymasks;
-            const uint32_t clean = special | anymask;  // 0: CLEAN
+            const uint32_t clean = rdl(rsum, 10);  // 0: CLEAN (no flag in a field, no mask byte)
             {
                 // CLEAN region (every plane FULL: certified, every pixel in frame): one straight-line statement for the four planes,
                 // no EXEC write, no branch.  The reads of plane k + 1 follow the v_sad_u16s of plane k row by row into the same 8
@@ -573,6 +569,10 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
 #undef RX_RD
             }
             if (__builtin_expect(clean != 0u, 0)) {
+                const uint32_t special = (fld[0] | fld[1] | fld[2] | fld[3]) & 0xc000u;
+                // per plane: what is out of frame although the certificates hold (0: nothing -- with no flag in the field that is a FULL plane)
+                const uint32_t xmasks = rdl(rsum, 11), ymasks = rdl(rsum, 12);
+                const uint32_t anymask = xmasks | ymasks;
                 if (__builtin_expect(anymask != 0u, 0)) {
 #pragma unroll
                     for (int k = 0; k < RX_KW; k++)
@@ -648,9 +648,10 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
                     uintptr_t coldp = (uintptr_t)a.cold;
                     asm volatile("" : "+s"(coldp));  // not loop-invariant for the optimiser: fetched here, not held in SGPRs over the loop
                     const int dpad = RX_COLD(coldp, int, dpad);
+                    const int v = RX_COLD(coldp, int, v0) + a.vcount - vleft;
                     const cu32 xt = as_const<cu32>(RX_COLD(coldp, const uint32_t *, xt) + ((size_t)tx * a.V + v) * dpad + chunk * RX_PC + wave * RX_KW);
                     const cu32 yt = as_const<cu32>(RX_COLD(coldp, const uint32_t *, yt) + ((size_t)ty * a.V + v) * dpad + chunk * RX_PC + wave * RX_KW);
-                    const uint32_t xsx = rdl(x0r, 6), yn = rdl(y0r, 3);
+                    const uint32_t xsx = rdl(rsum, 13), yn = rdl(rsum, 14);
                     const int x0 = (int)((xsx & 0xffffu) >> 2), y0 = (int)((yn >> 8) & 0x3fffu);
                     const bool staged = (xsx >> 16) != 0u && (yn & 0xffu) != 0u;
 #pragma unroll
@@ -720,7 +721,7 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
         }
 
         // ---- chunk epilogue ----
-        if (v + 1 == vend) {
+        if (--vleft == 0) {
             const int d0 = chunk * RX_PC + wave * RX_KW;
             const size_t P = (size_t)a.W * a.H;
             const uint32_t pix0 = 4u * (uint32_t)(row0 * a.W + col);  // byte offset of this lane's first pixel inside a plane
@@ -770,23 +771,15 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
 #pragma unroll
                 for (int j = 0; j < 8; j++) acc[j][k] = 0u;
             spacc = 0u;
-        }
-
-        if (++v == vend) {
-            v = a.v0;
+            vleft = a.vcount;
             chunk++;
         }
-        x0r = x1r;
-        y0r = y1r;
-        x1r = x2r;
-        y1r = y2r;
-        const uint32_t sw = slot_cur;
-        slot_cur = slot_nxt;
-        slot_nxt = sw;
+        slot_cur ^= slot_bytes;
     }
 
     // ---- depth selection across the four wavefronts (each holds the best of its own planes): lowest cost, ties -> lowest plane ----
     if (FUSED) {
+        wait_vm<0>();     // (the last turn's copy fetched nothing, but it is a copy)
         __syncthreads();  // every copy has landed and every sample loop is done: the slots are free
         uint2 *ex = (uint2 *)smem;  // [wave][row][lane]
 #pragma unroll
@@ -847,9 +840,9 @@ static RectSizes rect_sizes(const SweepParams &q)
     z.nw = (size_t)q.V * dpad;
     z.nxb = (size_t)q.tiles_x * q.V * q.nchunks;
     z.nyb = (size_t)q.tiles_y * q.V * q.nchunks;
-    z.nxw = z.nxb * 32;
-    z.nyr = z.nyb * 32;
-    z.total = 16 + z.nxw + z.nyr + 2 * z.nx + 2 * z.ny + z.nw + z.nxb + z.nyb + 64;  // + slack: prefetches read whole 8-dword lanes past a Y record
+    z.nxw = z.nxb * 4 * RX_REC;  // (a launch over fewer views packs its records into the front of the same tables)
+    z.nyr = z.nyb * 4 * RX_REC;
+    z.total = 16 + z.nxw + z.nyr + 2 * z.nx + 2 * z.ny + z.nw + z.nxb + z.nyb + 4 * RX_REC;  // + slack: the last turn's prefetch reads one region past the last Y record
     return z;
 }
 
@@ -934,8 +927,12 @@ int sweep_rect_plan(mvs_ctx *ctx, PlanHook *between)
     ctx->rect_rs = rs;
     ctx->rect_slot_dw = instrs * 256;
     ctx->rect_dpad = rt.dpad;
-    plan_rect_pack<<<(unsigned)((4 * nb + 255) / 256), 256, 0, ctx->stream>>>(q, rt, rs);
+    // the records in the order of a launch over all views and all chunks, one workgroup per tile (sweep_rect_launch packs them again
+    // for the order it walks them in, if that is another)
+    const RectOrder order = {0, q.V, 0, q.nchunks, q.nchunks};
+    plan_rect_pack<<<(unsigned)((4 * nb + 255) / 256), 256, 0, ctx->stream>>>(q, rt, rs, order, 1);
     MVS_HIP(ctx, hipGetLastError());
+    ctx->rect_order = {order.v0, order.vcount, order.chunk0, order.chunk1, order.cps};
     if (ctx->hooks.rect_verbose) {
         // which region bodies the sweep kernel will run.  CLEAN regions (tile, chunk, view, wavefront): no flag in the four fields and
         // no mask byte, in the X record of the tile column and in the Y record of the tile row.  Per (region, plane) of the others:
@@ -946,33 +943,33 @@ int sweep_rect_plan(mvs_ctx *ctx, PlanHook *between)
         MVS_HIP(ctx, hipMemcpyAsync(xw.data(), rt.xw, z.nxw * 4, hipMemcpyDeviceToHost, ctx->stream));
         MVS_HIP(ctx, hipMemcpyAsync(yr.data(), rt.yr, z.nyr * 4, hipMemcpyDeviceToHost, ctx->stream));
         MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const size_t per = (size_t)q.V * q.nchunks * 4;  // records per tile column / tile row
+        const size_t per = (size_t)q.V * q.nchunks * 4;  // records per tile column / tile row (the same order in both tables)
         const double TX = q.tiles_x, TY = q.tiles_y;
         double clean = 0.0, none = 0.0, flagged = 0.0, side[4] = {0.0, 0.0, 0.0, 0.0};
         for (size_t e = 0; e < per; e++) {
             size_t cx = 0, cy = 0;
             for (int t = 0; t < q.tiles_x; t++) {
-                const uint32_t *r = xw.data() + ((size_t)t * per + e) * 8;
-                cx += ((r[0] | r[1]) & 0x40004000u) == 0u && r[7] == 0u;
+                const uint32_t *r = xw.data() + ((size_t)t * per + e) * RX_REC;
+                cx += r[10] == 0u;
             }
             for (int t = 0; t < q.tiles_y; t++) {
-                const uint32_t *r = yr.data() + ((size_t)t * per + e) * 8;
-                cy += ((r[0] | r[1]) & 0x80008000u) == 0u && r[4] == 0u;
+                const uint32_t *r = yr.data() + ((size_t)t * per + e) * RX_REC;
+                cy += r[10] == 0u;
             }
             clean += (double)cx * (double)cy;
             for (int k = 0; k < RX_KW; k++) {
                 double xn = 0, xf = 0, yn = 0, yf = 0, l = 0, rt_ = 0, tp = 0, bt = 0;
                 for (int t = 0; t < q.tiles_x; t++) {
-                    const uint32_t *r = xw.data() + ((size_t)t * per + e) * 8;
-                    const uint32_t f = (r[k >> 1] >> (16 * (k & 1))) & 0xffffu, m = (r[7] >> (8 * k)) & 0xffu;
+                    const uint32_t *r = xw.data() + ((size_t)t * per + e) * RX_REC;
+                    const uint32_t f = r[k], m = (r[11] >> (8 * k)) & 0xffu;
                     xf += (f & 0x4000u) != 0u;
                     xn += (m & 0x40u) != 0u;
                     l += m != 0u && !(m & 0x40u) && !(m & 0x80u);
                     rt_ += m != 0u && !(m & 0x40u) && (m & 0x80u);
                 }
                 for (int t = 0; t < q.tiles_y; t++) {
-                    const uint32_t *r = yr.data() + ((size_t)t * per + e) * 8;
-                    const uint32_t f = (r[k >> 1] >> (16 * (k & 1))) & 0xffffu, m = (r[4] >> (8 * k)) & 0xffu;
+                    const uint32_t *r = yr.data() + ((size_t)t * per + e) * RX_REC;
+                    const uint32_t f = r[k], m = (r[12] >> (8 * k)) & 0xffu;
                     yf += (f & 0x8000u) != 0u;
                     yn += m == 0xffu;
                     tp += m != 0u && m != 0xffu && (m & 1u);
@@ -986,6 +983,22 @@ int sweep_rect_plan(mvs_ctx *ctx, PlanHook *between)
                 side[3] += bt * TX;
             }
         }
+        // the copies: instructions per region (all four wavefronts' / the most one wavefront issues) and, over the boxes that are not
+        // empty, how many lanes of a box's last instruction fetch something (the others are dropped by the range check; 64 = all)
+        int live_lo = 65, live_hi = 0, inst_lo = 1 << 30, inst_hi = 0;
+        unsigned long long live_set = 0ull;  // bit l - 1: some box's last instruction has l lanes that fetch
+        for (size_t e = 0; e < (size_t)q.tiles_y * per; e += 4) {
+            const int rows = (int)(yr[e * RX_REC + 14] & 0xffu), n = rows * units;
+            if (!rows) continue;
+            const int live = n % 64 ? n % 64 : 64;
+            live_set |= 1ull << (live - 1);
+            live_lo = live < live_lo ? live : live_lo;
+            live_hi = live > live_hi ? live : live_hi;
+            inst_lo = div_up(n, 64) < inst_lo ? div_up(n, 64) : inst_lo;
+            inst_hi = div_up(n, 64) > inst_hi ? div_up(n, 64) : inst_hi;
+        }
+        fprintf(stderr, "sweep_rect_plan: copies: row stride %d, %d instructions per region (%d per wavefront); boxes need %d to %d, "
+                "last instruction %d to %d lanes (set 0x%016llx)\n", rs, instrs, div_up(instrs, 4), inst_lo, inst_hi, live_lo, live_hi, live_set);
         const double nreg = (double)per * TX * TY, npl = nreg * RX_KW;
         fprintf(stderr, "sweep_rect_plan: clean regions %.2f %% of %.0f; planes: nothing in frame %.3f %%, failed certificate %.3f %%, "
                 "border left %.3f %% right %.3f %% top %.3f %% bottom %.3f %%\n", 100.0 * clean / nreg, nreg, 100.0 * none / npl,
@@ -1005,7 +1018,7 @@ int sweep_rect_plan(mvs_ctx *ctx, PlanHook *between)
     cold.invW = q.invW;
     cold.invH = q.invH;
     cold.dpad = rt.dpad;
-    cold.pad_ = 0;
+    cold.v0 = 0;
     ctx->rect_cold_host.resize(sizeof(RectCold));
     memcpy(ctx->rect_cold_host.data(), &cold, sizeof(RectCold));
     ctx->rect_ok = true;
@@ -1039,6 +1052,7 @@ int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsign
     cold.depth = (float *)ctx->depth.ptr;
     cold.cost = (float *)ctx->cost.ptr;
     cold.index = (int *)ctx->index.ptr;
+    cold.v0 = p.v0;
     if (!ctx->rect_cold_sent || memcmp(&cold, ctx->rect_cold_host.data(), sizeof(RectCold)) != 0) {
         memcpy(ctx->rect_cold_host.data(), &cold, sizeof(RectCold));
         MVS_HIP(ctx, hipMemcpyAsync(cold_dev, ctx->rect_cold_host.data(), sizeof(RectCold), hipMemcpyHostToDevice, ctx->stream));
@@ -1078,6 +1092,14 @@ int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsign
     a.cps = p.cps;
     const int nsplit = div_up(nch, p.cps);
     int rc;
+    // the records in the order this launch's workgroups walk them (plan_rect_pack); kept until a launch asks for another
+    const std::array<int, 5> order = {p.v0, p.vcount, p.chunk0, p.chunk1, p.cps};
+    if (order != ctx->rect_order) {
+        const size_t nb = (size_t)(p.tiles_x + p.tiles_y) * p.V * p.nchunks;
+        plan_rect_pack<<<(unsigned)((4 * nb + 255) / 256), 256, 0, ctx->stream>>>(p, rt, ctx->rect_rs, RectOrder{p.v0, p.vcount, p.chunk0, p.chunk1, p.cps}, 0);
+        MVS_HIP(ctx, hipGetLastError());
+        ctx->rect_order = order;
+    }
     if (fused && nsplit > 1) {
         if ((rc = ensure(ctx, ctx->best_parts, (size_t)nsplit * ctx->W * ctx->H * sizeof(uint2)))) return rc;
         p.part = (uint2 *)ctx->best_parts.ptr;
