@@ -216,6 +216,23 @@ int mvs_sweep_argmin(mvs_ctx *ctx);
  * The plane step is what makes two samplers that pick neighbouring planes of equal cost differ by 1/D in depth; refined depths of the
  * two samplers agree to a small fraction of it. */
 int mvs_sweep_refine_depth(mvs_ctx *ctx);
+/* Semi-global aggregation of the packed volume before depth selection (DESIGN.md section 13 is the arithmetic contract; exact integer
+ * arithmetic, bit-identical to tests/sgm_mirror.py).  Every cell's matching cost C = min(floor(16 mean cost), cost_cap) in 1/16 grey levels
+ * (a cell no view sees: cost_cap, and never selected) is aggregated along `paths` (4 or 8) image directions,
+ *   L_r(p, d) = C(p, d) + min(L_r(p - r, d), L_r(p - r, d -+ 1) + p1, min_k L_r(p - r, k) + p2) - min_k L_r(p - r, k),
+ * the sums S = sum_r L_r (uint16, [nplanes][H][W]) are kept on the device, and the context's depth / cost / index maps are rewritten from
+ * them: index = lowest plane with the smallest S among the seen cells, depth = z[index], cost = S / (16 paths) in grey levels; a pixel no
+ * view sees gets index -1, MVS_BACKGROUND_DEPTH, +inf (as mvs_sweep_argmin).  MVS_AGGREGATE_REFINE: the parabola of mvs_sweep_refine_depth
+ * on S.  Asynchronous on the context's stream, like mvs_sweep_argmin; reads the context's packed volume (its own or the caller's, either
+ * sampler) and does not modify it, so mvs_sweep_argmin afterwards restores the winner-take-all maps; everything that consumes the maps
+ * (mvs_sweep_fetch, mvs_sweep_depth_device, mvs_depth_upload_device ...) works unchanged.  Timed under MVS_K_ARGMIN.
+ * Errors: MVS_EINVAL for a NULL ctx, paths not 4 or 8, p1 < 0, p2 < p1, cost_cap outside 1..4080, paths (cost_cap + p2) > 65535, unknown
+ * flag bits, nplanes outside 2..256; MVS_ESTATE without planes or a packed volume; MVS_ENOMEM.  mvs_sweep_aggregated_device: S and its
+ * size (NULL before the first call).  mvs_sweep_aggregate_fetch synchronises and downloads S (diagnostic; MVS_ESTATE before the first call). */
+#define MVS_AGGREGATE_REFINE 1u
+int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, unsigned flags);
+void *mvs_sweep_aggregated_device(mvs_ctx *ctx, size_t *bytes);
+int mvs_sweep_aggregate_fetch(mvs_ctx *ctx, uint16_t *s_dhw);
 /* The same selection in two steps, for a view-sharded job that REDUCE-SCATTERS the packed volume instead of all-reducing it
  * (half the bytes over xGMI): rank r owns the summed cells of planes [plane_first, plane_first + plane_count) in
  * `volume_slice_dev` ([plane_count][H][W] u32) and selects a partial best per pixel over them -- `partial_out_dev` receives

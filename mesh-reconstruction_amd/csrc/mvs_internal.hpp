@@ -165,6 +165,10 @@ struct mvs_ctx {
     int tsdf_G = 0;
     float tsdf_origin[3] = {0.f, 0.f, 0.f};
     float tsdf_h = 0.f, tsdf_inv_tau = 0.f;
+    // semi-global aggregation (aggregate.hip: mvs_sweep_aggregate): the capped matching costs C and the path sums S, u16 [D][H][W] each;
+    // agg_planes = D of the last call (0: nothing aggregated yet)
+    mvs::DevBuf agg_cost, agg_sum;
+    int agg_planes = 0;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

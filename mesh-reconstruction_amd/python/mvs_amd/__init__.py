@@ -21,6 +21,7 @@ MVS_SWEEP_VOLUME = 1
 MVS_SWEEP_FUSED_ARGMIN = 2
 MVS_SWEEP_FORCE_GENERIC = 4
 MVS_SWEEP_NO_RECT = 8
+MVS_AGGREGATE_REFINE = 1
 MVS_SHARD_ROWS, MVS_SHARD_VIEWS, MVS_SHARD_VIEWS_SCATTER = 0, 1, 2
 SHARD_MODES = {"rows": 0, "views": 1, "views_scatter": 2}
 MVS_SAMPLER_FIXED, MVS_SAMPLER_EXACT_F32 = 0, 1
@@ -92,6 +93,9 @@ ABI = [
     ("mvs_tsdf_surface", _i, [_vp, _i, _vp]),
     ("mvs_sweep_argmin", _i, [_vp]),
     ("mvs_sweep_refine_depth", _i, [_vp]),
+    ("mvs_sweep_aggregate", _i, [_vp, _i, _i, _i, _i, C.c_uint]),
+    ("mvs_sweep_aggregated_device", _vp, [_vp, C.POINTER(_sz)]),
+    ("mvs_sweep_aggregate_fetch", _i, [_vp, C.POINTER(C.c_uint16)]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
     ("mvs_sweep_combine_partials", _i, [_vp, _vp, _i]),
     ("mvs_sweep_volume_device", _vp, [_vp, C.POINTER(_sz)]),
@@ -808,6 +812,30 @@ class Context:
 
     def sweep_argmin(self):
         self._check(self.lib.mvs_sweep_argmin(self.h))
+
+    def sweep_aggregate(self, paths=8, p1=16, p2=128, cost_cap=4080, refine=False):
+        """mvs_sweep_aggregate: semi-global aggregation of the packed volume along 4 or 8 paths, then depth selection over the sums
+        (rewrites the depth / cost / index maps; asynchronous, stream-ordered)"""
+        self._check(self.lib.mvs_sweep_aggregate(self.h, int(paths), int(p1), int(p2), int(cost_cap), MVS_AGGREGATE_REFINE if refine else 0))
+
+    def sweep_aggregate_fetch(self):
+        """mvs_sweep_aggregate_fetch -> S (D, H, W) uint16 of the last sweep_aggregate (synchronises)"""
+        n = _sz(0)
+        self.lib.mvs_sweep_aggregated_device(self.h, C.byref(n))
+        if not n.value:   # nothing aggregated yet: the library's answer (MVS_ESTATE)
+            self._check(self.lib.mvs_sweep_aggregate_fetch(self.h, None))
+            raise MvsError("sweep_aggregate_fetch: nothing aggregated yet")
+        s = np.empty((n.value // (2 * self.H * self.W), self.H, self.W), np.uint16)
+        self._check(self.lib.mvs_sweep_aggregate_fetch(self.h, _ptr(s, C.POINTER(C.c_uint16))))
+        return s
+
+    def sweep_aggregated_device(self):
+        """(device address, bytes) of S, [D][H][W] uint16; raises before the first sweep_aggregate"""
+        n = _sz(0)
+        p = self.lib.mvs_sweep_aggregated_device(self.h, C.byref(n))
+        if not p:
+            raise MvsError("nothing aggregated yet (sweep_aggregate first)")
+        return p, n.value
 
     def sweep_argmin_partial(self, volume_slice_ptr, plane_first, plane_count, partial_out_ptr):
         self._check(self.lib.mvs_sweep_argmin_partial(self.h, C.c_void_p(volume_slice_ptr), int(plane_first), int(plane_count),
