@@ -66,6 +66,29 @@ def path_costs(C, dy, dx, p1, p2):
     return L
 
 
+def winners(C, dy, dx, p1, p2):
+    """which term of rule 2 gave L_r(p, d), int8 [D, H, W]: 0 the start of a path (p - r outside the image), 1 the own plane, 2 plane
+    d - 1 plus P1, 3 plane d + 1 plus P1, 4 m + P2, -1 where the smallest term is not unique.  Derived from path_costs, and checked
+    against it cell by cell."""
+    C = np.asarray(C, np.int64)
+    D, H, W = C.shape
+    L = path_costs(C, dy, dx, p1, p2)
+    ys, xs = np.arange(H) - dy, np.arange(W) - dx
+    inside = ((ys >= 0) & (ys < H))[:, None] & ((xs >= 0) & (xs < W))[None, :]
+    prev = L[:, np.clip(ys, 0, H - 1)][:, :, np.clip(xs, 0, W - 1)]   # L_r(p - r, .), garbage where p - r is outside
+    m = prev.min(axis=0, keepdims=True)
+    absent = np.int64(1) << 40
+    terms = np.full((4,) + C.shape, absent, np.int64)
+    terms[0] = prev
+    terms[1, 1:] = prev[:-1] + p1
+    terms[2, :-1] = prev[1:] + p1
+    terms[3] = m + p2
+    least = terms.min(axis=0)
+    assert (np.where(inside[None], C + least - m, C) == L).all()
+    code = np.where((terms == least[None]).sum(axis=0) == 1, terms.argmin(axis=0) + 1, -1)
+    return np.where(inside[None], code, 0).astype(np.int8)
+
+
 def aggregate(C, paths, p1, p2):
     """rule 3: S = sum of L_r over the first `paths` directions, uint16 [D, H, W]"""
     assert paths in (4, 8)
