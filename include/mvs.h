@@ -345,6 +345,40 @@ int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cos
 int mvs_tsdf_fetch(mvs_ctx *ctx, float *sdf_sum /* G^3, nullable */, int32_t *count /* G^3, nullable */);
 int mvs_tsdf_surface(mvs_ctx *ctx, int min_observations /* >= 1 */, struct mvs_surface **out);
 
+/* ---- ray-cast of the TSDF volume: the fused model as depth and normal maps of any camera (csrc/raycast.hip) ----
+ * mvs_tsdf_raycast marches one ray per pixel of the context's W x H frame through the volume's field F (rule 5 above, with this call's
+ * min_observations) and writes the first front-face crossing of its zero level set: NDC z of `cam` in the library's depth convention
+ * (1.0 = empty) and the unit normal +grad F (toward free space, like the mesh's faces; (0, 0, 0) = empty).  Every pixel is written on every
+ * call; the maps hold the last raycast (mvs_tsdf_volume and mvs_depth_store do not touch them) and stay in HBM:
+ * mvs_depth_upload_device(ctx, slot, cam, mvs_tsdf_raycast_depth_device(ctx), NULL) stores the model's depth map device to device.
+ * `cam` is any projective camera with a finite centre (it need not be a stored one); P, P^-1 and the centre C are those of a depth slot
+ * (mvs_depth_slot_matrices).  All f32, one rounding per operation, no contraction; inv_h = 1 / h and delta = step_nodes h rounded once
+ * on the host, K_max = floor(1.75 (G - 1) / step_nodes) + 2:
+ *   1 ray: X1 = P^-1 (xn, yn, 0, 1) dehomogenised (xn / yn the sweep's pixel centres), (P (X1, 1)).w > 0; d = X1 - C,
+ *     len = sqrt((dx^2 + dy^2) + dz^2) finite and > 0, d = d / len
+ *   2 box: per axis lo = o_a, hi = o_a + h (float)(G - 1); d_a != 0: the slab between (lo - C_a) / d_a and (hi - C_a) / d_a; d_a = 0: unbounded
+ *     when lo <= C_a <= hi, else empty; t_in = max(0, near ends), t_out = min(far ends); empty unless t_in <= t_out
+ *   3 samples k = 0 .. K_max while t_k = t_in + delta (float)k <= t_out: X = C + t_k d, g = (X - o) inv_h, cell i_a = clamp(floor(g_a), 0, G - 2)
+ *     (NaN: 0), fraction f_a = clamp(g_a - (float)i_a, 0, 1) (NaN: 0); valid when the cell's mask is set; value: the trilinear interpolant of
+ *     the cell's 8 corners of F, each lerp a + f (b - a), along i, then j, then k
+ *   4 hit: the first k >= 1 with sample k - 1 valid and > 0 and sample k valid and <= 0; t* = t_(k-1) + delta (F_(k-1) / (F_(k-1) - F_k)).
+ *     Back faces (<= 0 to > 0) are ignored; a ray that starts behind a surface leaves it without a hit
+ *   5 at X* = C + t* d: cell and fractions as in 3, empty if its mask is clear; gradient of the interpolant (per axis the 4 corner differences
+ *     along it, lerped along the other two in the order i, j, k), n = g / sqrt((gx^2 + gy^2) + gz^2) (length finite and > 0);
+ *     z = (P (X*, 1)).z / (P (X*, 1)).w, empty unless -1 < z < 1 (a hit nearer than the near plane has no value in the depth convention)
+ * A surface is missed where step_nodes h exceeds the band observed behind it (the truncation): keep step_nodes <= truncation / (2 h).
+ * mvs_tsdf_raycast is asynchronous and stream-ordered like mvs_tsdf_integrate and timed under MVS_K_TSDF; mvs_tsdf_raycast_fetch
+ * synchronises.  mvs_tsdf_upload is the counterpart of mvs_tsdf_fetch (checkpoint and resume; crafted fields): it replaces both fields
+ * and synchronises; values are taken as given (a count below min_observations is "unobserved" wherever that is tested).
+ * Errors: MVS_EINVAL for a NULL ctx, cam or (upload) array, a camera with a non-finite entry, singular or without a finite centre,
+ * min_observations < 1, step_nodes not finite or outside [1/16, 4]; MVS_ESTATE before mvs_tsdf_volume, and for mvs_tsdf_raycast_fetch
+ * before the first raycast; MVS_ENOMEM. */
+int mvs_tsdf_upload(mvs_ctx *ctx, const float *sdf_sum /* G^3 */, const int32_t *count /* G^3 */);
+int mvs_tsdf_raycast(mvs_ctx *ctx, const float cam[16], int min_observations /* >= 1 */, float step_nodes /* 1/16 .. 4 */);
+void *mvs_tsdf_raycast_depth_device(mvs_ctx *ctx);   /* H*W f32, NDC z of cam, 1.0 = empty; NULL before the first raycast */
+void *mvs_tsdf_raycast_normals_device(mvs_ctx *ctx); /* H*W*3 f32, unit, (0,0,0) = empty; NULL before the first raycast */
+int mvs_tsdf_raycast_fetch(mvs_ctx *ctx, float *depth_hw /* nullable */, float *normals_hw3 /* nullable */);
+
 /* ---- one main view on several GPUs of one node (SURVEY.md section 8b "multi-GPU", 8e, north_star) -----------------------------
  * A communicator owns one context per listed device and one RCCL communicator across them (librccl is loaded when the first
  * communicator is created; the library has no link dependency on it).  mvs_sweep_sharded runs ONE main view on all of them, one host
@@ -425,7 +459,7 @@ int mvs_comm_device(const mvs_comm *comm, int rank);
 #define MVS_K_PROJECT 4
 #define MVS_K_FLOW 5
 #define MVS_K_FUSE 6 /* mvs_fuse_depth: count pass, scan, row pass */
-#define MVS_K_TSDF 7 /* mvs_tsdf_integrate: w-map passes and integration launches */
+#define MVS_K_TSDF 7 /* mvs_tsdf_integrate: w-map passes and integration launches; mvs_tsdf_raycast: field, brick mask, ray kernel */
 #define MVS_K_COUNT 8
 int mvs_profile_enable(mvs_ctx *ctx, int on);
 /* synchronises, then returns summed elapsed ms and launch count per kernel class since the last reset */

@@ -162,8 +162,10 @@ __global__ __launch_bounds__(256) void fuse_rows_kernel(const FuseArgs a, const 
     fuse_body<true>(a, nullptr, offsets, rows);
 }
 
+}  // namespace
+
 // P^-1 by invert4 in double, rounded once; C = null vector of rows x, y, w of P (the signed 3 x 3 minors, as extractCameraCenter takes
-// it), dehomogenised in double and rounded once
+// it), dehomogenised in double and rounded once.  (Declared in mvs_internal.hpp: mvs_tsdf_raycast derives its camera the same way.)
 bool slot_matrices(const float cam[16], mvs_ctx::DepthSlot &s)
 {
     double m[16], mi[16];
@@ -191,6 +193,8 @@ bool slot_matrices(const float cam[16], mvs_ctx::DepthSlot &s)
     s.C[3] = 1.0f;
     return true;
 }
+
+namespace {
 
 int depth_upload_impl(mvs_ctx *ctx, int slot, const float cam[16], const float *depth, const float *cost, bool device)
 {

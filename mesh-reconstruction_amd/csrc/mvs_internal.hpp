@@ -165,6 +165,13 @@ struct mvs_ctx {
     int tsdf_G = 0;
     float tsdf_origin[3] = {0.f, 0.f, 0.f};
     float tsdf_h = 0.f, tsdf_inv_tau = 0.f;
+    // ray-cast of the volume (raycast.hip: mvs_tsdf_raycast): tsdf_work holds the field F and cell mask of tsdf_field_key's min_observations
+    // (0: stale; mvs_tsdf_surface writes it too), tsdf_bricks the brick bitmask made from that field for tsdf_brick_key (0: stale);
+    // the W x H depth map and normal map of the last raycast
+    int tsdf_field_key = 0, tsdf_brick_key = 0;
+    mvs::DevBuf tsdf_bricks, ray_depth, ray_normals;
+    bool ray_have = false;
+    bool ray_plain = false;          // test hook mvs_test_raycast_plain: march without the brick mask (timing A/B, tests)
     // semi-global aggregation (aggregate.hip: mvs_sweep_aggregate): the capped matching costs C and the path sums S, u16 [D][H][W] each;
     // agg_planes = D of the last call (0: nothing aggregated yet)
     mvs::DevBuf agg_cost, agg_sum;
@@ -204,6 +211,11 @@ struct ProfileScope {
 void invert4(const double m[16], double out[16]);
 void view_matrix(const float main_cam[16], const float side_cam[16], int W, int H, float Q[12]);
 void plane_table(int D, float z_lo, float z_hi, float *z);
+// fuse.hip: the matrices of a depth slot from its camera (P, P^-1 and the centre); false for a camera with a
+// non-finite entry, a singular one, or one without a finite centre.  mvs_tsdf_raycast takes its camera through it too.
+bool slot_matrices(const float cam[16], mvs_ctx::DepthSlot &s);
+// tsdf.hip: F and the cell mask of the volume for min_obs into ctx->tsdf_work, unless they are there already (launches on ctx->stream)
+int tsdf_ensure_field(mvs_ctx *ctx, int min_obs);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 

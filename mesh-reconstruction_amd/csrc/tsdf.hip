@@ -11,6 +11,8 @@
 //                          FuseArgs does); the node's (sum, count) is read once, updated by the chunk's slots in list order, written once.
 //                          No atomics, no LDS: the result is the same bytes however the list is split into calls or chunks.
 // mvs_tsdf_surface: tsdf_field_kernel turns (sum, count) into F and the cell support mask, then the shared mesher runs on ctx->stream.
+// The field is kept (tsdf_ensure_field) until the volume changes; mvs_tsdf_raycast (csrc/raycast.hip) reads it too.  mvs_tsdf_upload is the
+// counterpart of mvs_tsdf_fetch: it replaces both fields by the caller's.
 //
 // Arithmetic: f32, one rounding per operation, no contraction (the library builds with -ffp-contract=off; the pixel centres' fmaf is the
 // sweep's and is written out); tests/tsdf_mirror.py restates it in numpy, bit for bit.
@@ -132,6 +134,29 @@ __global__ __launch_bounds__(256) void tsdf_field_kernel(int G, const float *__r
 
 }  // namespace
 
+// F and the cell mask for min_obs in ctx->tsdf_work (5 bytes per node).  tsdf_field_key names the min_observations they were made for
+// (0: stale -- the volume changed); mvs_tsdf_surface and mvs_tsdf_raycast both come through here, so neither sees the other's field.
+int tsdf_ensure_field(mvs_ctx *ctx, int min_obs)
+{
+    const int G = ctx->tsdf_G;
+    const size_t N3 = (size_t)G * G * G;
+    const size_t had = ctx->tsdf_work.bytes;
+    int rc;
+    if ((rc = ensure(ctx, ctx->tsdf_work, 5 * N3))) {
+        ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;
+        return rc;
+    }
+    if (ctx->tsdf_work.bytes != had) ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;  // a new buffer
+    if (ctx->tsdf_field_key == min_obs) return MVS_OK;
+    ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;
+    const float *sum = (const float *)ctx->tsdf_vol.ptr;
+    float *F = (float *)ctx->tsdf_work.ptr;
+    tsdf_field_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, ctx->stream>>>(G, sum, (const int *)(sum + N3), min_obs, F, (unsigned char *)(F + N3));
+    MVS_HIP(ctx, hipGetLastError());
+    ctx->tsdf_field_key = min_obs;
+    return MVS_OK;
+}
+
 }  // namespace mvs
 
 using namespace mvs;
@@ -151,6 +176,7 @@ int mvs_tsdf_volume(mvs_ctx *ctx, int nodes_per_axis, const float origin3[3], fl
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N3 = (size_t)G * G * G;
     ctx->tsdf_G = 0;  // no volume until the new one is allocated and cleared
+    ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;
     int rc;
     if ((rc = ensure(ctx, ctx->tsdf_vol, 8 * N3))) return rc;
     MVS_HIP(ctx, hipMemsetAsync(ctx->tsdf_vol.ptr, 0, 8 * N3, ctx->stream));
@@ -208,6 +234,7 @@ int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cos
     ia.halfH = (float)H * 0.5f;
     ia.inv_tau = ctx->tsdf_inv_tau;
     const dim3 igrid((unsigned)div_up(G, kTsdfTX), (unsigned)div_up(G, kTsdfTY), (unsigned)G);
+    ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;  // the field of the old volume is stale
     ProfileScope ps(ctx, MVS_K_TSDF);
     for (int e0 = 0; e0 < nslots; e0 += kTsdfChunk) {
         const int n = nslots - e0 < kTsdfChunk ? nslots - e0 : kTsdfChunk;
@@ -243,6 +270,21 @@ int mvs_tsdf_fetch(mvs_ctx *ctx, float *sdf_sum, int32_t *count)
     return MVS_OK;
 }
 
+int mvs_tsdf_upload(mvs_ctx *ctx, const float *sdf_sum, const int32_t *count)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_upload: null context");
+    if (!sdf_sum || !count) return fail(ctx, MVS_EINVAL, "mvs_tsdf_upload: null array");
+    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "mvs_tsdf_upload: no volume (mvs_tsdf_volume first)");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N3 = (size_t)ctx->tsdf_G * ctx->tsdf_G * ctx->tsdf_G;
+    float *sum = (float *)ctx->tsdf_vol.ptr;
+    ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;
+    MVS_HIP(ctx, hipMemcpyAsync(sum, sdf_sum, N3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    MVS_HIP(ctx, hipMemcpyAsync(sum + N3, count, N3 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MVS_OK;
+}
+
 int mvs_tsdf_surface(mvs_ctx *ctx, int min_observations, mvs_surface **out)
 {
     if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_surface: null context");
@@ -254,12 +296,9 @@ int mvs_tsdf_surface(mvs_ctx *ctx, int min_observations, mvs_surface **out)
     const int G = ctx->tsdf_G;
     const size_t N3 = (size_t)G * G * G;
     int rc;
-    if ((rc = ensure(ctx, ctx->tsdf_work, 5 * N3))) return rc;
-    const float *sum = (const float *)ctx->tsdf_vol.ptr;
+    if ((rc = tsdf_ensure_field(ctx, min_observations))) return rc;
     float *F = (float *)ctx->tsdf_work.ptr;
     unsigned char *mask = (unsigned char *)(F + N3);
-    tsdf_field_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, ctx->stream>>>(G, sum, (const int *)(sum + N3), min_observations, F, mask);
-    MVS_HIP(ctx, hipGetLastError());
     mvs_surface *res = new (std::nothrow) mvs_surface;
     if (!res) return fail(ctx, MVS_ENOMEM, "mvs_tsdf_surface: host allocation failed");
     res->grid.G = G;

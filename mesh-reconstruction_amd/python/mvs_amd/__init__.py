@@ -91,6 +91,11 @@ ABI = [
     ("mvs_tsdf_integrate", _i, [_vp, _i, _i32p, _f]),
     ("mvs_tsdf_fetch", _i, [_vp, _fp, _i32p]),
     ("mvs_tsdf_surface", _i, [_vp, _i, _vp]),
+    ("mvs_tsdf_upload", _i, [_vp, _fp, _i32p]),
+    ("mvs_tsdf_raycast", _i, [_vp, _fp, _i, _f]),
+    ("mvs_tsdf_raycast_depth_device", _vp, [_vp]),
+    ("mvs_tsdf_raycast_normals_device", _vp, [_vp]),
+    ("mvs_tsdf_raycast_fetch", _i, [_vp, _fp, _fp]),
     ("mvs_sweep_argmin", _i, [_vp]),
     ("mvs_sweep_refine_depth", _i, [_vp]),
     ("mvs_sweep_aggregate", _i, [_vp, _i, _i, _i, _i, C.c_uint]),
@@ -173,6 +178,9 @@ def load_library(path=None):
     if hasattr(lib, "mvs_test_onecall_bands"):
         lib.mvs_test_onecall_bands.restype = _i
         lib.mvs_test_onecall_bands.argtypes = [_vp]
+    if hasattr(lib, "mvs_test_raycast_plain"):
+        lib.mvs_test_raycast_plain.restype = _i
+        lib.mvs_test_raycast_plain.argtypes = [_vp, _i]
     _lib = lib
     return lib
 
@@ -801,6 +809,42 @@ class Context:
         finally:
             self.lib.mvs_surface_free(s)
         return v, f
+
+    def tsdf_upload(self, sdf_sum, count):
+        """mvs_tsdf_upload: replace the volume's fields by sum [G, G, G] f32 and count [G, G, G] i32, indexed [k][j][i] (synchronises)"""
+        G = getattr(self, "_tsdf_G", 0)
+        if not G:   # no volume made through this object: the library's answer (MVS_ESTATE before mvs_tsdf_volume)
+            one_f, one_i = np.zeros(1, np.float32), np.zeros(1, np.int32)
+            self._check(self.lib.mvs_tsdf_upload(self.h, _ptr(one_f, _fp), _ptr(one_i, _i32p)))
+            raise MvsError("tsdf_upload: the volume was not made with tsdf_volume")
+        s = _f32(sdf_sum, (G, G, G))
+        c = np.ascontiguousarray(count, np.int32)
+        if c.shape != (G, G, G):
+            raise ValueError("count must be [%d, %d, %d]" % (G, G, G))
+        try:
+            self._check(self.lib.mvs_tsdf_upload(self.h, _ptr(s, _fp), _ptr(c, _i32p)))
+        finally:
+            self._depth_keep = {}
+
+    def tsdf_raycast(self, cam, min_observations=1, step=0.5, fetch=True):
+        """mvs_tsdf_raycast: the volume's zero level set as seen by `cam` -> (depth [H, W] f32 NDC z, 1.0 = empty; normals [H, W, 3] f32,
+        unit, zeros = empty).  step: the march's step in node spacings (keep it <= truncation / (2 h)).  fetch=False: queue the raycast only
+        (asynchronous; the maps stay on the device: tsdf_raycast_pointers) and return None"""
+        c = _f32(cam, (4, 4))
+        self._check(self.lib.mvs_tsdf_raycast(self.h, _ptr(c, _fp), int(min_observations), float(step)))
+        if not fetch:
+            return None
+        d = np.empty((self.H, self.W), np.float32)
+        n = np.empty((self.H, self.W, 3), np.float32)
+        try:
+            self._check(self.lib.mvs_tsdf_raycast_fetch(self.h, _ptr(d, _fp), _ptr(n, _fp)))
+        finally:
+            self._depth_keep = {}
+        return d, n
+
+    def tsdf_raycast_pointers(self):
+        """device addresses (depth H*W f32, normals H*W*3 f32) of the last raycast; (0, 0) before the first"""
+        return self.lib.mvs_tsdf_raycast_depth_device(self.h) or 0, self.lib.mvs_tsdf_raycast_normals_device(self.h) or 0
 
     def depth_device_array(self):
         """zero-copy [H, W] f32 view of the device depth map for torch.as_tensor(..., device='cuda') (valid until the
