@@ -379,6 +379,50 @@ void *mvs_tsdf_raycast_depth_device(mvs_ctx *ctx);   /* H*W f32, NDC z of cam, 1
 void *mvs_tsdf_raycast_normals_device(mvs_ctx *ctx); /* H*W*3 f32, unit, (0,0,0) = empty; NULL before the first raycast */
 int mvs_tsdf_raycast_fetch(mvs_ctx *ctx, float *depth_hw /* nullable */, float *normals_hw3 /* nullable */);
 
+/* ---- appearance of the TSDF volume: the frames' grey levels fused beside the distances (csrc/tsdf.hip, csrc/appearance.hip, DESIGN.md
+ * section 15) ----  The volume can carry what the surface looks like: the frames of the frame store (mvs_frame_upload; one u8 per pixel)
+ * vote their intensities into it while their depth maps are integrated, and the result is read back at the surface points of any depth
+ * map (mvs_tsdf_shade: the image that goes with mvs_tsdf_raycast's depth and normals, comparable with a frame by mvs_compare) or at a
+ * caller's points (mvs_tsdf_sample_appearance: vertex grey levels of mvs_tsdf_surface's mesh).  Integer votes, f32 reads with one rounding
+ * per operation and no contraction:
+ *   A cell: one uint32 per node in the volume's node order, count << 24 | sum: count 0..255 votes, sum of their u8 intensities
+ *     (<= 255 * 255); 4 bytes per node.  The appearance volume is allocated and zeroed by the first mvs_tsdf_integrate_frames or
+ *     mvs_tsdf_appearance_upload after mvs_tsdf_volume; mvs_tsdf_volume drops it ("no appearance"); mvs_tsdf_integrate and mvs_tsdf_upload
+ *     do not touch it.  A caller who never asks for appearance allocates nothing.
+ *   B mvs_tsdf_integrate_frames takes the pairs (depth_slots[e], frame_slots[e]) in list order: rules 1-4 of mvs_tsdf_integrate on
+ *     (sum, count), the same bytes as mvs_tsdf_integrate(ctx, n, depth_slots, max_cost) gives; and where rule 4 updates with t < 1 (so
+ *     -1 <= t < 1: the unclamped band around the observed surface) and the cell's count is < 255: sum += I[r][c], count += 1, with I the
+ *     raw frame in frame-store slot frame_slots[e] and (r, c) the pixel of rule 3.  A cell at count 255 ignores later votes (list order
+ *     is fixed: deterministic); a pair listed twice votes twice; a list split over calls gives the same bytes.
+ *   C appearance at a point X: g_a = (X_a - o_a) inv_h (inv_h = 1 / h rounded once); every 0 <= g_a <= (float)(G - 1) (NaN fails), else
+ *     none: no clamping into the box.  Cell and fractions as in the raycast's rule 3; corner d = dk 4 + dj 2 + di has weight
+ *     w_d = (wx wy) wz, wx = di ? fx : 1 - fx (wy, wz alike), and is present when its count > 0 with a_d = (float)sum_d / (float)count_d;
+ *     over the present corners in ascending d: num = num + w_d a_d, den = den + w_d, both from 0; none unless den > 0, else num / den.
+ *     Independent of F, of the cell mask and of min_observations.
+ *   D mvs_tsdf_shade(ctx, cam, depth_dev): depth_dev is H*W f32 on the context's GPU in the library's depth convention for cam
+ *     (mvs_tsdf_raycast_depth_device, mvs_sweep_depth_device, mvs_depth_slot_device, ...); P and P^-1 are a depth slot's for cam.  Per
+ *     pixel: -1 < z < 1 (fusion rule 1), X = P^-1 (xn, yn, z, 1) dehomogenised with the sweep's pixel centres (fusion rule 2),
+ *     (P (X, 1)).w > 0, then C.  Output H*W pairs of u8 like mvs_warp_by_depth's: (min(floor(value + 0.5), 255), 255), or (0, 0) where
+ *     any of that fails; every pixel is written.  Asynchronous and stream-ordered; the map stays in HBM (mvs_tsdf_shade_device: NULL
+ *     before the first shade); mvs_tsdf_shade_fetch synchronises.
+ *   E mvs_tsdf_sample_appearance(ctx, points4, n, out): host rows (x, y, z, w) as mvs_surface_fetch returns them; X = (x / w, y / w, z / w),
+ *     then C; out[i] is the value, NaN for none.  Synchronises.
+ *   F mvs_tsdf_appearance_fetch / _upload: the G^3 cells, the counterparts of mvs_tsdf_fetch / mvs_tsdf_upload (checkpoint; crafted
+ *     fields); upload takes values as given (a sum above 255 * count is the caller's affair) and both synchronise.
+ * Errors: MVS_EINVAL for a NULL ctx or array, n < 1, a depth slot outside the depth store, a frame slot outside the frame store, a negative
+ * or NaN max_cost, a camera mvs_tsdf_raycast would refuse, a NULL depth_dev; MVS_ESTATE before mvs_tsdf_volume, for an unfilled depth or
+ * frame slot, a finite max_cost with a slot stored without cost, for _appearance_fetch, _shade and _sample_appearance while there is no
+ * appearance volume, and for mvs_tsdf_shade_fetch before the first shade; MVS_ENOMEM.  All launches are timed under MVS_K_TSDF.
+ * mvs_depth_slot_device: the device address of a filled depth slot's H*W f32 map (NULL for an unfilled slot or one outside the store). */
+int mvs_tsdf_integrate_frames(mvs_ctx *ctx, int n, const int *depth_slots, const int *frame_slots, float max_cost /* INFINITY: costs not read */);
+int mvs_tsdf_appearance_fetch(mvs_ctx *ctx, uint32_t *cells /* G^3 */);
+int mvs_tsdf_appearance_upload(mvs_ctx *ctx, const uint32_t *cells /* G^3 */);
+int mvs_tsdf_shade(mvs_ctx *ctx, const float cam[16], const void *depth_dev /* H*W f32 on the context's GPU */);
+void *mvs_tsdf_shade_device(mvs_ctx *ctx); /* H*W pairs of u8 (grey, 255) or (0, 0); NULL before the first shade */
+int mvs_tsdf_shade_fetch(mvs_ctx *ctx, uint8_t *shaded_hw2);
+int mvs_tsdf_sample_appearance(mvs_ctx *ctx, const float *points4 /* n x 4 */, int n, float *out /* n */);
+void *mvs_depth_slot_device(mvs_ctx *ctx, int slot);
+
 /* ---- one main view on several GPUs of one node (SURVEY.md section 8b "multi-GPU", 8e, north_star) -----------------------------
  * A communicator owns one context per listed device and one RCCL communicator across them (librccl is loaded when the first
  * communicator is created; the library has no link dependency on it).  mvs_sweep_sharded runs ONE main view on all of them, one host
@@ -459,7 +503,7 @@ int mvs_comm_device(const mvs_comm *comm, int rank);
 #define MVS_K_PROJECT 4
 #define MVS_K_FLOW 5
 #define MVS_K_FUSE 6 /* mvs_fuse_depth: count pass, scan, row pass */
-#define MVS_K_TSDF 7 /* mvs_tsdf_integrate: w-map passes and integration launches; mvs_tsdf_raycast: field, brick mask, ray kernel */
+#define MVS_K_TSDF 7 /* mvs_tsdf_integrate: w-map passes and integration launches; mvs_tsdf_raycast: field, brick mask, ray kernel; mvs_tsdf_integrate_frames, _shade, _sample_appearance */
 #define MVS_K_COUNT 8
 int mvs_profile_enable(mvs_ctx *ctx, int on);
 /* synchronises, then returns summed elapsed ms and launch count per kernel class since the last reset */

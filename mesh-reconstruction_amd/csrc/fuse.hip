@@ -261,6 +261,12 @@ int mvs_depth_slot_matrices(const mvs_ctx *ctx, int slot, float out[36])
     return MVS_OK;
 }
 
+void *mvs_depth_slot_device(mvs_ctx *ctx, int slot)
+{
+    if (!ctx || slot < 0 || slot >= (int)ctx->dstore.size() || !ctx->dstore[slot].have) return nullptr;
+    return (float *)ctx->dstore_depth.ptr + (size_t)ctx->W * ctx->H * slot;
+}
+
 int mvs_fuse_depth(mvs_ctx *ctx, int ref_slot, int nneighbours, const int *neighbour_slots, int min_consistent, float max_reproj_px, float max_rel_depth,
                    float max_cost, float *out_points7, int *out_count)
 {

@@ -172,6 +172,12 @@ struct mvs_ctx {
     mvs::DevBuf tsdf_bricks, ray_depth, ray_normals;
     bool ray_have = false;
     bool ray_plain = false;          // test hook mvs_test_raycast_plain: march without the brick mask (timing A/B, tests)
+    // appearance of the volume (tsdf.hip: mvs_tsdf_integrate_frames; appearance.hip: mvs_tsdf_shade / mvs_tsdf_sample_appearance): one packed
+    // u32 cell per node (count << 24 | sum of u8 intensities), there only while tsdf_app_have (mvs_tsdf_volume drops it; the first
+    // mvs_tsdf_integrate_frames or mvs_tsdf_appearance_upload after it makes a zeroed one); the W x H map of u8 pairs of the last shade; the
+    // points and values of one mvs_tsdf_sample_appearance
+    mvs::DevBuf tsdf_app, shade_map, app_points;
+    bool tsdf_app_have = false, shade_have = false;
     // semi-global aggregation (aggregate.hip: mvs_sweep_aggregate): the capped matching costs C and the path sums S, u16 [D][H][W] each;
     // agg_planes = D of the last call (0: nothing aggregated yet)
     mvs::DevBuf agg_cost, agg_sum;
@@ -216,6 +222,8 @@ void plane_table(int D, float z_lo, float z_hi, float *z);
 bool slot_matrices(const float cam[16], mvs_ctx::DepthSlot &s);
 // tsdf.hip: F and the cell mask of the volume for min_obs into ctx->tsdf_work, unless they are there already (launches on ctx->stream)
 int tsdf_ensure_field(mvs_ctx *ctx, int min_obs);
+// tsdf.hip: the appearance volume, allocated and zeroed unless it is there (ctx->tsdf_app_have)
+int tsdf_ensure_appearance(mvs_ctx *ctx);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 

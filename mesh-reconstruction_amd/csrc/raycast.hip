@@ -16,6 +16,7 @@
 // Arithmetic: f32, one rounding per operation, no contraction (-ffp-contract=off); tests/raycast_mirror.py restates it in numpy, bit for bit.
 #include "depth_rules.hpp"
 #include "mvs_internal.hpp"
+#include "volume_rules.hpp"   // rule 3's cell_axis
 
 #include <cmath>
 
@@ -42,16 +43,6 @@ struct Cell {
     int ix, iy, iz, base;
     float fx, fy, fz;
 };
-
-// rule 3: cell index clamp(floor(g), 0, G - 2) and fraction clamp(g - (float)i, 0, 1); a NaN gives 0 for both
-__device__ __forceinline__ int cell_axis(float g, int G, float &f)
-{
-    const float fl = floorf(g);
-    const int i = fl >= 0.f ? (fl <= (float)(G - 2) ? (int)fl : G - 2) : 0;
-    const float r = g - (float)i;
-    f = r > 0.f ? (r < 1.f ? r : 1.f) : 0.f;
-    return i;
-}
 
 __device__ __forceinline__ float3 ray_point(const RayArgs &a, float3 d, float t) { return make_float3(a.C[0] + t * d.x, a.C[1] + t * d.y, a.C[2] + t * d.z); }
 

@@ -14,6 +14,12 @@
 // The field is kept (tsdf_ensure_field) until the volume changes; mvs_tsdf_raycast (csrc/raycast.hip) reads it too.  mvs_tsdf_upload is the
 // counterpart of mvs_tsdf_fetch: it replaces both fields by the caller's.
 //
+// mvs_tsdf_integrate_frames is the same pair of launches with the frames' intensities carried along:
+//   tsdf_wmap_frames_kernel       the w-map pass writing 8-byte records (w, intensity of that pixel in the listed frame-store slot);
+//   tsdf_integrate_frames_kernel  the same loop with one 8-byte gather per (node, slot); besides (sum, count) the node's packed appearance
+//                                 cell (count << 24 | sum of u8 intensities) is read once, voted into where -1 <= t < 1, written once.
+// Both pairs share their bodies (wmap_value, integrate_node<bool>), so the TSDF fields come out the same bytes either way.
+//
 // Arithmetic: f32, one rounding per operation, no contraction (the library builds with -ffp-contract=off; the pixel centres' fmaf is the
 // sweep's and is written out); tests/tsdf_mirror.py restates it in numpy, bit for bit.
 #include "depth_rules.hpp"
@@ -43,18 +49,20 @@ struct WmapArgs {
     float invW, invH, max_cost;
 };
 
+struct FrameArgs {
+    const uint8_t *raw[kTsdfChunk];          // mvs_tsdf_integrate_frames: the raw frame (frame store) paired with each listed depth slot
+};
+
 struct IntegrateArgs {
-    const float *wmap;                       // the chunk's w-maps, W*H apart, in list order
+    const float *wmap;                       // the chunk's w-maps (or 8-byte records), W*H apart, in list order
     float P[kTsdfChunk][12];                 // rows x, y, w of P
     int n, W, H, G;
     float ox, oy, oz, h, halfW, halfH, inv_tau;
 };
 
-__global__ __launch_bounds__(256) void tsdf_wmap_kernel(const WmapArgs a)
+// contract step 1 for pixel p = (r, c) of the chunk's slot s
+__device__ __forceinline__ float wmap_value(const WmapArgs &a, int s, int p, int r, int c)
 {
-    const int p = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
-    if (p >= a.W * a.H) return;
-    const int r = p / a.W, c = p - r * a.W;
     float w = __builtin_nanf("");
     const float z = a.depth[s][p];
     if (depth_valid(z, a.cost[s], (size_t)p, a.use_cost, a.max_cost)) {
@@ -63,10 +71,33 @@ __global__ __launch_bounds__(256) void tsdf_wmap_kernel(const WmapArgs a)
         const float ws = prow(a.Pw[s], 0, unproject(a.Pi[s], xn, yn, z));
         if (ws > 0.f) w = ws;
     }
-    a.wmap[(size_t)s * a.W * a.H + p] = w;
+    return w;
 }
 
-__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs a, float *__restrict__ sum, int *__restrict__ count)
+__global__ __launch_bounds__(256) void tsdf_wmap_kernel(const WmapArgs a)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (p >= a.W * a.H) return;
+    const int r = p / a.W, c = p - r * a.W;
+    a.wmap[(size_t)s * a.W * a.H + p] = wmap_value(a, s, p, r, c);
+}
+
+// the same pass with the frame's intensity beside w: a.wmap holds 8-byte records (w, (float bits of) the u8 intensity), so the integration
+// loop fetches both with one gather; the frame is read here, coalesced, once per pixel
+__global__ __launch_bounds__(256) void tsdf_wmap_frames_kernel(const WmapArgs a, const FrameArgs f)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (p >= a.W * a.H) return;
+    const int r = p / a.W, c = p - r * a.W;
+    const float w = wmap_value(a, s, p, r, c);
+    reinterpret_cast<float2 *>(a.wmap)[(size_t)s * a.W * a.H + p] = make_float2(w, __uint_as_float((uint32_t)f.raw[s][p]));
+}
+
+// contract steps 2-4 for one node and the chunk's slots in list order.  APP: a.wmap holds tsdf_wmap_frames_kernel's records and the node's
+// appearance cell takes the intensity wherever the update falls into the unclamped band -1 <= t < 1 (DESIGN.md section 15 rule B); the
+// (sum, count) arithmetic is the same statements either way
+template <bool APP>
+__device__ __forceinline__ void integrate_node(const IntegrateArgs &a, float *__restrict__ sum, int *__restrict__ count, uint32_t *__restrict__ cells)
 {
     const int i = blockIdx.x * kTsdfTX + (int)(threadIdx.x & (kTsdfTX - 1));
     const int j = blockIdx.y * kTsdfTY + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kTsdfTX));  // (one wave = one row: uniform)
@@ -77,14 +108,18 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
     const size_t P = (size_t)a.W * a.H;
     float s = sum[node];
     int c = count[node];
+    uint32_t cell = 0;
+    if (APP) cell = cells[node];
     // kTsdfBatch slots at a time: first every gather of the batch is issued, then the updates run in list order (a slot with nothing to
     // say -- behind the camera, outside the frame, no depth there -- reads as NaN), so a wave waits for one batch of loads, not for each
     for (int e0 = 0; e0 < a.n; e0 += kTsdfBatch) {
         float qw[kTsdfBatch], wd[kTsdfBatch];
+        uint32_t in[kTsdfBatch];
 #pragma unroll
         for (int b = 0; b < kTsdfBatch; b++) {
             wd[b] = __builtin_nanf("");
             qw[b] = 0.f;
+            in[b] = 0;
             if (e0 + b >= a.n) continue;
             const float *M = a.P[e0 + b];
             qw[b] = M[8] * x + ((M[9] * y + M[10] * z) + M[11]);
@@ -96,7 +131,14 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
             const float v = (1.0f - qy * inv) * a.halfH - 0.5f;
             const float fc = floorf(u + 0.5f), fr = floorf(v + 0.5f);
             if (!(fc >= 0.f && fc < (float)a.W && fr >= 0.f && fr < (float)a.H)) continue;  // (NaN fails too)
-            wd[b] = a.wmap[P * (e0 + b) + (size_t)((int)fr * a.W + (int)fc)];
+            const size_t at = P * (e0 + b) + (size_t)((int)fr * a.W + (int)fc);
+            if (APP) {
+                const float2 rec = reinterpret_cast<const float2 *>(a.wmap)[at];
+                wd[b] = rec.x;
+                in[b] = __float_as_uint(rec.y);
+            } else {
+                wd[b] = a.wmap[at];
+            }
         }
 #pragma unroll
         for (int b = 0; b < kTsdfBatch; b++) {
@@ -105,11 +147,24 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
             if (t >= -1.0f) {
                 s = s + (t < 1.0f ? t : 1.0f);
                 c = c + 1;
+                if (APP && t < 1.0f && cell < 0xFF000000u) cell += 0x01000000u + in[b];  // one vote: count + 1, sum + I (sum <= 255 * 255)
             }
         }
     }
     sum[node] = s;
     count[node] = c;
+    if (APP) cells[node] = cell;
+}
+
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs a, float *__restrict__ sum, int *__restrict__ count)
+{
+    integrate_node<false>(a, sum, count, nullptr);
+}
+
+__global__ __launch_bounds__(256) void tsdf_integrate_frames_kernel(const IntegrateArgs a, float *__restrict__ sum, int *__restrict__ count,
+                                                                    uint32_t *__restrict__ cells)
+{
+    integrate_node<true>(a, sum, count, cells);
 }
 
 // F = sum / count where count >= min_obs, else 1; mask[node] = 1 when the cell with that low corner has all 8 corners observed enough
@@ -157,63 +212,55 @@ int tsdf_ensure_field(mvs_ctx *ctx, int min_obs)
     return MVS_OK;
 }
 
-}  // namespace mvs
-
-using namespace mvs;
-
-extern "C" {
-
-int mvs_tsdf_volume(mvs_ctx *ctx, int nodes_per_axis, const float origin3[3], float node_spacing, float truncation)
+// the appearance volume (section 15 rule A): G^3 packed cells, allocated and zeroed when it is first asked for after mvs_tsdf_volume
+int tsdf_ensure_appearance(mvs_ctx *ctx)
 {
-    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_volume: null context");
-    if (!origin3) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: origin is null");
-    const int G = nodes_per_axis;
-    if (G < kTsdfMinG || G > kTsdfMaxG) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: nodes_per_axis %d out of range %d..%d", G, kTsdfMinG, kTsdfMaxG);
-    for (int c = 0; c < 3; c++)
-        if (!std::isfinite(origin3[c])) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: origin is not finite");
-    if (!(node_spacing > 0.f && node_spacing < INFINITY) || !(truncation > 0.f && truncation < INFINITY))
-        return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: node_spacing %g and truncation %g must be finite and > 0", node_spacing, truncation);
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t N3 = (size_t)G * G * G;
-    ctx->tsdf_G = 0;  // no volume until the new one is allocated and cleared
-    ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;
+    if (ctx->tsdf_app_have) return MVS_OK;
+    const size_t N3 = (size_t)ctx->tsdf_G * ctx->tsdf_G * ctx->tsdf_G;
     int rc;
-    if ((rc = ensure(ctx, ctx->tsdf_vol, 8 * N3))) return rc;
-    MVS_HIP(ctx, hipMemsetAsync(ctx->tsdf_vol.ptr, 0, 8 * N3, ctx->stream));
-    ctx->tsdf_G = G;
-    for (int c = 0; c < 3; c++) ctx->tsdf_origin[c] = origin3[c];
-    ctx->tsdf_h = node_spacing;
-    ctx->tsdf_inv_tau = 1.0f / truncation;  // rounded once (contract step 4)
+    if ((rc = ensure(ctx, ctx->tsdf_app, N3 * sizeof(uint32_t)))) return rc;
+    MVS_HIP(ctx, hipMemsetAsync(ctx->tsdf_app.ptr, 0, N3 * sizeof(uint32_t), ctx->stream));
+    ctx->tsdf_app_have = true;
     return MVS_OK;
 }
 
-int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cost)
+namespace {
+
+// mvs_tsdf_integrate (frames = false: frame_slots is not looked at) and mvs_tsdf_integrate_frames
+int tsdf_integrate_impl(mvs_ctx *ctx, const char *who, int nslots, const int *slots, const int *frame_slots, bool frames, float max_cost)
 {
-    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_integrate: null context");
-    if (!slots) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: slots is null");
-    if (nslots < 1) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: nslots %d < 1", nslots);
-    if (!(max_cost >= 0.f)) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: max_cost %g must be >= 0", max_cost);
-    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "mvs_tsdf_integrate: no volume (mvs_tsdf_volume first)");
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
+    if (!slots || (frames && !frame_slots)) return fail(ctx, MVS_EINVAL, "%s: slots is null", who);
+    if (nslots < 1) return fail(ctx, MVS_EINVAL, "%s: nslots %d < 1", who, nslots);
+    if (!(max_cost >= 0.f)) return fail(ctx, MVS_EINVAL, "%s: max_cost %g must be >= 0", who, max_cost);
+    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "%s: no volume (mvs_tsdf_volume first)", who);
     const int cap = (int)ctx->dstore.size();
     for (int e = 0; e < nslots; e++)
-        if (slots[e] < 0 || slots[e] >= cap) return fail(ctx, MVS_EINVAL, "mvs_tsdf_integrate: slot %d outside the depth store (capacity %d)", slots[e], cap);
+        if (slots[e] < 0 || slots[e] >= cap) return fail(ctx, MVS_EINVAL, "%s: slot %d outside the depth store (capacity %d)", who, slots[e], cap);
+    for (int e = 0; frames && e < nslots; e++)
+        if (frame_slots[e] < 0 || frame_slots[e] >= ctx->store_cap)
+            return fail(ctx, MVS_EINVAL, "%s: frame slot %d outside the frame store (capacity %d)", who, frame_slots[e], ctx->store_cap);
     const bool use_cost = max_cost < INFINITY;
     for (int e = 0; e < nslots; e++) {
         const mvs_ctx::DepthSlot &s = ctx->dstore[slots[e]];
-        if (!s.have) return fail(ctx, MVS_ESTATE, "mvs_tsdf_integrate: slot %d holds no depth map (mvs_depth_upload)", slots[e]);
-        if (use_cost && !s.have_cost) return fail(ctx, MVS_ESTATE, "mvs_tsdf_integrate: max_cost %g is finite but slot %d was stored without a cost map", max_cost, slots[e]);
+        if (!s.have) return fail(ctx, MVS_ESTATE, "%s: slot %d holds no depth map (mvs_depth_upload)", who, slots[e]);
+        if (use_cost && !s.have_cost) return fail(ctx, MVS_ESTATE, "%s: max_cost %g is finite but slot %d was stored without a cost map", who, max_cost, slots[e]);
+        if (frames && !ctx->store_have[(size_t)frame_slots[e]]) return fail(ctx, MVS_ESTATE, "%s: frame slot %d holds no frame (mvs_frame_upload)", who, frame_slots[e]);
     }
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const int W = ctx->W, H = ctx->H, G = ctx->tsdf_G;
     const size_t P = (size_t)W * H, N3 = (size_t)G * G * G;
     int rc;
-    if ((rc = ensure(ctx, ctx->tsdf_wmaps, (size_t)(nslots < kTsdfChunk ? nslots : kTsdfChunk) * P * sizeof(float)))) return rc;
+    if ((rc = ensure(ctx, ctx->tsdf_wmaps, (size_t)(nslots < kTsdfChunk ? nslots : kTsdfChunk) * P * (frames ? sizeof(float2) : sizeof(float))))) return rc;
+    if (frames && (rc = tsdf_ensure_appearance(ctx))) return rc;
     float *wmaps = (float *)ctx->tsdf_wmaps.ptr;
     float *sum = (float *)ctx->tsdf_vol.ptr;
     int *count = (int *)(sum + N3);
     WmapArgs wa;
+    FrameArgs fa;
     IntegrateArgs ia;
     memset(&wa, 0, sizeof(wa));
+    memset(&fa, 0, sizeof(fa));
     memset(&ia, 0, sizeof(ia));
     wa.wmap = wmaps;
     wa.W = W;
@@ -247,14 +294,65 @@ int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cos
             memcpy(wa.Pi[e], s.Pi, sizeof(s.Pi));
             memcpy(ia.P[e], s.P, 8 * sizeof(float));           // rows x, y
             memcpy(ia.P[e] + 8, s.P + 12, 4 * sizeof(float));  // row w
+            if (frames) fa.raw[e] = (const uint8_t *)ctx->store_raw.ptr + P * frame_slots[e0 + e];
         }
         ia.n = n;
-        tsdf_wmap_kernel<<<dim3((unsigned)div_up((int)P, 256), (unsigned)n), 256, 0, ctx->stream>>>(wa);
-        MVS_HIP(ctx, hipGetLastError());
-        tsdf_integrate_kernel<<<igrid, kTsdfTX * kTsdfTY, 0, ctx->stream>>>(ia, sum, count);
+        const dim3 wgrid((unsigned)div_up((int)P, 256), (unsigned)n);
+        if (frames) {
+            tsdf_wmap_frames_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa, fa);
+            MVS_HIP(ctx, hipGetLastError());
+            tsdf_integrate_frames_kernel<<<igrid, kTsdfTX * kTsdfTY, 0, ctx->stream>>>(ia, sum, count, (uint32_t *)ctx->tsdf_app.ptr);
+        } else {
+            tsdf_wmap_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa);
+            MVS_HIP(ctx, hipGetLastError());
+            tsdf_integrate_kernel<<<igrid, kTsdfTX * kTsdfTY, 0, ctx->stream>>>(ia, sum, count);
+        }
         MVS_HIP(ctx, hipGetLastError());
     }
     return MVS_OK;
+}
+
+}  // namespace
+
+}  // namespace mvs
+
+using namespace mvs;
+
+extern "C" {
+
+int mvs_tsdf_volume(mvs_ctx *ctx, int nodes_per_axis, const float origin3[3], float node_spacing, float truncation)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_volume: null context");
+    if (!origin3) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: origin is null");
+    const int G = nodes_per_axis;
+    if (G < kTsdfMinG || G > kTsdfMaxG) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: nodes_per_axis %d out of range %d..%d", G, kTsdfMinG, kTsdfMaxG);
+    for (int c = 0; c < 3; c++)
+        if (!std::isfinite(origin3[c])) return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: origin is not finite");
+    if (!(node_spacing > 0.f && node_spacing < INFINITY) || !(truncation > 0.f && truncation < INFINITY))
+        return fail(ctx, MVS_EINVAL, "mvs_tsdf_volume: node_spacing %g and truncation %g must be finite and > 0", node_spacing, truncation);
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N3 = (size_t)G * G * G;
+    ctx->tsdf_G = 0;  // no volume until the new one is allocated and cleared
+    ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;
+    ctx->tsdf_app_have = false;  // and no appearance: the first mvs_tsdf_integrate_frames / mvs_tsdf_appearance_upload makes a zeroed one
+    int rc;
+    if ((rc = ensure(ctx, ctx->tsdf_vol, 8 * N3))) return rc;
+    MVS_HIP(ctx, hipMemsetAsync(ctx->tsdf_vol.ptr, 0, 8 * N3, ctx->stream));
+    ctx->tsdf_G = G;
+    for (int c = 0; c < 3; c++) ctx->tsdf_origin[c] = origin3[c];
+    ctx->tsdf_h = node_spacing;
+    ctx->tsdf_inv_tau = 1.0f / truncation;  // rounded once (contract step 4)
+    return MVS_OK;
+}
+
+int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cost)
+{
+    return tsdf_integrate_impl(ctx, "mvs_tsdf_integrate", nslots, slots, nullptr, false, max_cost);
+}
+
+int mvs_tsdf_integrate_frames(mvs_ctx *ctx, int n, const int *depth_slots, const int *frame_slots, float max_cost)
+{
+    return tsdf_integrate_impl(ctx, "mvs_tsdf_integrate_frames", n, depth_slots, frame_slots, true, max_cost);
 }
 
 int mvs_tsdf_fetch(mvs_ctx *ctx, float *sdf_sum, int32_t *count)
@@ -281,6 +379,33 @@ int mvs_tsdf_upload(mvs_ctx *ctx, const float *sdf_sum, const int32_t *count)
     ctx->tsdf_field_key = ctx->tsdf_brick_key = 0;
     MVS_HIP(ctx, hipMemcpyAsync(sum, sdf_sum, N3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     MVS_HIP(ctx, hipMemcpyAsync(sum + N3, count, N3 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MVS_OK;
+}
+
+int mvs_tsdf_appearance_fetch(mvs_ctx *ctx, uint32_t *cells)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_appearance_fetch: null context");
+    if (!cells) return fail(ctx, MVS_EINVAL, "mvs_tsdf_appearance_fetch: cells is null");
+    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "mvs_tsdf_appearance_fetch: no volume (mvs_tsdf_volume first)");
+    if (!ctx->tsdf_app_have) return fail(ctx, MVS_ESTATE, "mvs_tsdf_appearance_fetch: no appearance volume (mvs_tsdf_integrate_frames or mvs_tsdf_appearance_upload first)");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N3 = (size_t)ctx->tsdf_G * ctx->tsdf_G * ctx->tsdf_G;
+    MVS_HIP(ctx, hipMemcpyAsync(cells, ctx->tsdf_app.ptr, N3 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MVS_OK;
+}
+
+int mvs_tsdf_appearance_upload(mvs_ctx *ctx, const uint32_t *cells)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_tsdf_appearance_upload: null context");
+    if (!cells) return fail(ctx, MVS_EINVAL, "mvs_tsdf_appearance_upload: cells is null");
+    if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "mvs_tsdf_appearance_upload: no volume (mvs_tsdf_volume first)");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N3 = (size_t)ctx->tsdf_G * ctx->tsdf_G * ctx->tsdf_G;
+    int rc;
+    if ((rc = tsdf_ensure_appearance(ctx))) return rc;
+    MVS_HIP(ctx, hipMemcpyAsync(ctx->tsdf_app.ptr, cells, N3 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MVS_OK;
 }

@@ -96,6 +96,14 @@ ABI = [
     ("mvs_tsdf_raycast_depth_device", _vp, [_vp]),
     ("mvs_tsdf_raycast_normals_device", _vp, [_vp]),
     ("mvs_tsdf_raycast_fetch", _i, [_vp, _fp, _fp]),
+    ("mvs_tsdf_integrate_frames", _i, [_vp, _i, _i32p, _i32p, _f]),
+    ("mvs_tsdf_appearance_fetch", _i, [_vp, _u32p]),
+    ("mvs_tsdf_appearance_upload", _i, [_vp, _u32p]),
+    ("mvs_tsdf_shade", _i, [_vp, _fp, _vp]),
+    ("mvs_tsdf_shade_device", _vp, [_vp]),
+    ("mvs_tsdf_shade_fetch", _i, [_vp, _u8p]),
+    ("mvs_tsdf_sample_appearance", _i, [_vp, _fp, _i, _fp]),
+    ("mvs_depth_slot_device", _vp, [_vp, _i]),
     ("mvs_sweep_argmin", _i, [_vp]),
     ("mvs_sweep_refine_depth", _i, [_vp]),
     ("mvs_sweep_aggregate", _i, [_vp, _i, _i, _i, _i, C.c_uint]),
@@ -845,6 +853,75 @@ class Context:
     def tsdf_raycast_pointers(self):
         """device addresses (depth H*W f32, normals H*W*3 f32) of the last raycast; (0, 0) before the first"""
         return self.lib.mvs_tsdf_raycast_depth_device(self.h) or 0, self.lib.mvs_tsdf_raycast_normals_device(self.h) or 0
+
+    # ---- appearance of the TSDF volume --------------------------------------------------------------
+    def tsdf_integrate_frames(self, depth_slots, frame_slots, max_cost=float("inf")):
+        """mvs_tsdf_integrate_frames: mvs_tsdf_integrate of depth_slots, and frame-store slot frame_slots[e] votes its intensities into the
+        appearance volume along with depth_slots[e] (asynchronous, stream-ordered)"""
+        if len(depth_slots) != len(frame_slots):
+            raise ValueError("depth_slots and frame_slots must pair up")
+        ds = np.ascontiguousarray(np.asarray(list(depth_slots) if len(depth_slots) else [0], dtype=np.int32))
+        fs = np.ascontiguousarray(np.asarray(list(frame_slots) if len(frame_slots) else [0], dtype=np.int32))
+        self._check(self.lib.mvs_tsdf_integrate_frames(self.h, len(depth_slots), _ptr(ds, _i32p), _ptr(fs, _i32p), float(max_cost)))
+
+    def tsdf_appearance_fetch(self):
+        """mvs_tsdf_appearance_fetch -> cells [G, G, G] u32 (count << 24 | sum), indexed [k][j][i]"""
+        G = getattr(self, "_tsdf_G", 0)
+        if not G:
+            raise MvsError("tsdf_appearance_fetch: the volume was not made with tsdf_volume")
+        cells = np.empty((G, G, G), np.uint32)
+        try:
+            self._check(self.lib.mvs_tsdf_appearance_fetch(self.h, _ptr(cells, _u32p)))
+        finally:
+            self._depth_keep = {}
+        return cells
+
+    def tsdf_appearance_upload(self, cells):
+        """mvs_tsdf_appearance_upload: replace the appearance volume by cells [G, G, G] u32, indexed [k][j][i] (synchronises)"""
+        G = getattr(self, "_tsdf_G", 0)
+        if not G:
+            raise MvsError("tsdf_appearance_upload: the volume was not made with tsdf_volume")
+        c = np.ascontiguousarray(cells, np.uint32)
+        if c.shape != (G, G, G):
+            raise ValueError("cells must be [%d, %d, %d]" % (G, G, G))
+        try:
+            self._check(self.lib.mvs_tsdf_appearance_upload(self.h, _ptr(c, _u32p)))
+        finally:
+            self._depth_keep = {}
+
+    def tsdf_shade(self, cam, depth_ptr, fetch=True):
+        """mvs_tsdf_shade: the volume's appearance at the surface points of the device depth map at address depth_ptr (H*W f32 in `cam`'s
+        depth convention, e.g. tsdf_raycast_pointers()[0]) -> [H, W, 2] u8: (grey, 255), or (0, 0) where there is none.  fetch=False: queue
+        the launch only (asynchronous; the map stays on the device: tsdf_shade_pointer) and return None"""
+        c = _f32(cam, (4, 4))
+        self._check(self.lib.mvs_tsdf_shade(self.h, _ptr(c, _fp), C.c_void_p(int(depth_ptr)) if depth_ptr else None))
+        if not fetch:
+            return None
+        out = np.empty((self.H, self.W, 2), np.uint8)
+        try:
+            self._check(self.lib.mvs_tsdf_shade_fetch(self.h, _ptr(out, _u8p)))
+        finally:
+            self._depth_keep = {}
+        return out
+
+    def tsdf_shade_pointer(self):
+        """device address of the last shaded map (H*W pairs of u8); 0 before the first"""
+        return self.lib.mvs_tsdf_shade_device(self.h) or 0
+
+    def tsdf_sample_appearance(self, points):
+        """mvs_tsdf_sample_appearance: points [N, 4] rows (x, y, z, w), e.g. tsdf_surface's vertices -> [N] f32 grey levels, NaN = none"""
+        p = _f32(np.asarray(points, np.float32).reshape(-1, 4))
+        out = np.empty(len(p), np.float32)
+        one = np.zeros(4, np.float32)
+        try:
+            self._check(self.lib.mvs_tsdf_sample_appearance(self.h, _ptr(p if len(p) else one, _fp), len(p), _ptr(out if len(p) else one, _fp)))
+        finally:
+            self._depth_keep = {}
+        return out
+
+    def depth_slot_pointer(self, slot):
+        """device address of a filled depth slot's H*W f32 map (0: unfilled, or outside the store)"""
+        return self.lib.mvs_depth_slot_device(self.h, int(slot)) or 0
 
     def depth_device_array(self):
         """zero-copy [H, W] f32 view of the device depth map for torch.as_tensor(..., device='cuda') (valid until the
