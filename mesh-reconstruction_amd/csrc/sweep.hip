@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256, 3) void sweep_tiled(SweepParams p)
     __shared__ __attribute__((aligned(16))) uint2 lds[LDS_QUADS];
     __shared__ uint2 best_state[FUSED ? 256 * NPX : 1];  // (packed best cell, best index) per (pixel j, thread)
 
-    const int band_tile = (p.debug & 2) ? ((int)blockIdx.x < p.tiles_x * p.tyn ? (int)blockIdx.x : -1)
+    const int band_tile = (p.debug & DBG_LINEAR_TILES) ? ((int)blockIdx.x < p.tiles_x * p.tyn ? (int)blockIdx.x : -1)
                                         : grouped_tile(blockIdx.x, p.tiles_x, p.tyn);
     if (band_tile < 0) return;
     const int tx = band_tile % p.tiles_x, ty = band_tile / p.tiles_x + p.ty0;
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256, 3) void sweep_tiled(SweepParams p)
             const int rh = __builtin_amdgcn_readfirstlane((int)((desc.y >> 8) & 0xffu));
             const int rp = __builtin_amdgcn_readfirstlane((int)(desc.y >> 24) << 5);
             __syncthreads();  // all reads of the previous region are done
-            if (!(p.debug & 1)) stage_region_q16(p.quads16 + p.pad_slab * v, p.pitch, x0, y0, rw, rh, rp, lds);
+            if (!(p.debug & DBG_NO_STAGING)) stage_region_q16(p.quads16 + p.pad_slab * v, p.pitch, x0, y0, rw, rh, rp, lds);
             __syncthreads();
             RegionView rv;
             rv.lds_bytes = (const char *)lds;
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(256, 3) void sweep_tiled(SweepParams p)
                 // the low 32 bits of a generic pointer into LDS are the LDS byte address
                 int lds_minus_org8 = (int)(uint32_t)(uintptr_t)lds - rv.org8;
                 asm volatile("" : "+v"(lds_minus_org8));  // keep it in a VGPR so mul24 + add fuses into v_mad_i32_i24
-                if (bw == 0.0f && !(p.debug & 4)) {  // wave-uniform: plane-independent w (see sample_lds_pair)
+                if (bw == 0.0f && !(p.debug & DBG_NO_CONST_W)) {  // wave-uniform: plane-independent w (see sample_lds_pair)
 #pragma unroll
                     for (int j = 0; j < NPX; j++) {
                         if (ok[j]) {
@@ -460,9 +460,9 @@ __global__ __launch_bounds__(256, 3) void sweep_tiled(SweepParams p)
                             sample_chunk_pipelined<PC, true>(A, bx, by, bw, r_const, zc, rv.rp8, lds_minus_org8, (uint32_t)Im[j], acc[j]);
                         }
                     }
-                } else if (NPX == 2 && !(p.debug & 16)) {
+                } else if (NPX == 2 && !(p.debug & DBG_NO_PAIRED_READS)) {
                     // general cameras in the 2 x 32 shape (no spills): the hand-pipelined reads pay here too,
-                    // 2.54 -> 2.39 ms at c3 (tools/ab_general.py; debug bit 4 of the high byte forces the loop below)
+                    // 2.54 -> 2.39 ms at c3 (tools/ab_general.py; DBG_NO_PAIRED_READS forces the loop below)
 #pragma unroll
                     for (int j = 0; j < NPX; j++) {
                         if (ok[j]) {
@@ -604,6 +604,18 @@ __global__ __launch_bounds__(256) void combine_best(SweepParams p, int nsplit, s
     store_best<CS>(p, pix, best & ((1u << CS) - 1u), best >> CS, bi);
 }
 
+// host: that merge for a launch whose splits (choose_split) left their partial bests in p.part, over the launch's rows
+template <int CS>
+static int merge_split_bests(mvs_ctx *ctx, const SweepParams &p)
+{
+    if (!p.part) return MVS_OK;
+    const size_t first = (size_t)p.row_begin * p.W;
+    const size_t count = (size_t)(p.row_end - p.row_begin) * p.W;
+    combine_best<CS><<<(unsigned)((count + 255) / 256), 256, 0, ctx->stream>>>(p, split_count(p), first, count);
+    MVS_HIP(ctx, hipGetLastError());
+    return MVS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // depth selection over the packed volume
 // ------------------------------------------------------------------------------------------------------
@@ -712,14 +724,6 @@ __global__ void rcp_check_kernel(uint32_t exp_bits, unsigned long long *out)
     }
 }
 
-// sweep_fx.hip: the fixed-point sampler (contract v2)
-int sweep_fx_plan_general(mvs_ctx *ctx);
-int sweep_fx_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, bool generic, unsigned flags);
-int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsigned flags);
-int sweep_xrect_plan(mvs_ctx *ctx);  // sweep_xrect.hip: the exact sampler on rectified views
-int sweep_xrect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsigned flags);
-int warp_by_depth_fx_launch(mvs_ctx *ctx, const float *depth_dev, const float *q_dev, const uint8_t *pad_dev, int pitch, uint8_t *out2_dev);
-
 // defined in context.hip
 __global__ void pad_wrap_kernel(const uint8_t *__restrict__ img, uint8_t *__restrict__ pad, int W, int H, int pitch);
 
@@ -766,13 +770,17 @@ static int ensure_outputs(mvs_ctx *ctx, bool need_volume)
     return MVS_OK;
 }
 
-static int sweep_run_impl(mvs_ctx *ctx, int view_first, int view_count, int plane_first, int plane_count, int row_first,
-                          int row_count, unsigned flags);
+// the views, planes and rows of one sweep call
+struct SweepRange {
+    int view_first, view_count, plane_first, plane_count, row_first, row_count;
+};
+
+static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags);
 
 int mvs_sweep_run(mvs_ctx *ctx, int view_first, int view_count, unsigned flags)
 {
     if (!ctx) return MVS_EINVAL;
-    return sweep_run_impl(ctx, view_first, view_count, 0, ctx->D, 0, ctx->H, flags);
+    return sweep_run_impl(ctx, {view_first, view_count, 0, ctx->D, 0, ctx->H}, flags);
 }
 
 int mvs_sweep_run_rows(mvs_ctx *ctx, int view_first, int view_count, int row_first, int row_count, unsigned flags)
@@ -783,7 +791,7 @@ int mvs_sweep_run_rows(mvs_ctx *ctx, int view_first, int view_count, int row_fir
         ((row_first + row_count) % gran != 0 && row_first + row_count != ctx->H))
         return fail(ctx, MVS_EINVAL, "mvs_sweep_run_rows: row range [%d,%d) must lie in 0..%d and start/end on multiples of %d",
                     row_first, row_first + row_count, ctx->H, gran);
-    return sweep_run_impl(ctx, view_first, view_count, 0, ctx->D, row_first, row_count, flags);
+    return sweep_run_impl(ctx, {view_first, view_count, 0, ctx->D, row_first, row_count}, flags);
 }
 
 int mvs_sweep_row_granularity(void) { return ROW_GRAN; }
@@ -829,117 +837,105 @@ int mvs_sweep_run_planes(mvs_ctx *ctx, int view_first, int view_count, int plane
         ((plane_first + plane_count) % mvs_sweep_plane_granularity() != 0 && plane_first + plane_count != ctx->D))
         return fail(ctx, MVS_EINVAL, "mvs_sweep_run_planes: plane range [%d,%d) must lie in 0..%d and start/end on multiples of %d",
                     plane_first, plane_first + plane_count, ctx->D, mvs_sweep_plane_granularity());
-    return sweep_run_impl(ctx, view_first, view_count, plane_first, plane_count, 0, ctx->H, flags);
+    return sweep_run_impl(ctx, {view_first, view_count, plane_first, plane_count, 0, ctx->H}, flags);
 }
 
 int mvs_sweep_plane_granularity(void) { return PLANE_GRAN; }
 
-static int sweep_run_impl(mvs_ctx *ctx, int view_first, int view_count, int plane_first, int plane_count, int row_first,
-                          int row_count, unsigned flags)
+// launch of the exact sampler's general kernels: sweep_tiled in the shape `p` was filled for, or the un-tiled kernel
+static int sweep_tiled_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f)
 {
-    if (!ctx) return MVS_EINVAL;
-    if (!ctx->have_main || !ctx->have_views || !ctx->have_planes)
-        return fail(ctx, MVS_ESTATE, "mvs_sweep_run: set main view, side views and planes first");
-    if (view_first < 0 || view_count < 0 || view_first + view_count > ctx->V)
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_run: view range [%d,%d) outside 0..%d", view_first,
-                    view_first + view_count, ctx->V);
-    // Only the documented bits of `flags` reach the kernels.  Bits 8-23 carry timing-experiment switches (debug bits, forced plane-split
-    // count: tools/exp_*.py, tests) and are honoured only when the process sets MVS_DEBUG_FLAGS=1: a caller's stray high bits must not
-    // change tile order, look-ahead or split counts silently.
-    if (!ctx->hooks.debug_flags) flags &= (MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN | MVS_SWEEP_FORCE_GENERIC | MVS_SWEEP_NO_RECT);
-    const bool vol = flags & MVS_SWEEP_VOLUME, fused = flags & MVS_SWEEP_FUSED_ARGMIN;
-    if (!vol && !fused) return fail(ctx, MVS_EINVAL, "mvs_sweep_run: flags select neither volume nor fused argmin");
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_outputs(ctx, vol);
-    if (rc) return rc;
-
-    const bool generic = (flags & MVS_SWEEP_FORCE_GENERIC) != 0;
-    const int debug = (int)((flags >> 8) & 0xff);  // undocumented timing-experiment bits (bit 3: never use the 2 x 32 shape)
-    if (row_count <= 0 || plane_count <= 0) return MVS_OK;  // empty band or empty plane group: nothing to compute
-
-    if (ctx->sampler == MVS_SAMPLER_FIXED) {
-        if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "mvs_sweep_run: the fixed sampler's cells hold at most 255 views (have %d)", ctx->V);
-        // 1/256-texel coordinates live in the low 22 mantissa bits of a float in [2^23, 2^24): 256 * size + 132 must stay below 2^22
-        if (ctx->W > 16383 || ctx->H > 16383)
-            return fail(ctx, MVS_EINVAL, "mvs_sweep_run: the fixed sampler addresses images of up to 16383 x 16383 (have %d x %d); use MVS_SAMPLER_EXACT_F32",
-                        ctx->W, ctx->H);
-        if (ctx->plan_valid && ctx->plan_shape != 3) ctx->plan_valid = false;
-        if (!generic && !ctx->plan_valid && ctx->V > 0) {
-            ProfileScope ps(ctx, MVS_K_PLAN);
-            if ((rc = sweep_fx_plan(ctx))) return rc;
-            ctx->plan_shape = 3;
-            ctx->plan_valid = true;
-        }
-        if (generic && (rc = ensure_pads(ctx))) return rc;  // the un-tiled kernel gathers single texels of the padded frames
-        // (a run over zero views writes empty cells: the general kernel's job -- the rectified one iterates over regions)
-        const bool rect = ctx->rect_ok && !generic && ctx->V > 0 && view_count > 0 && !(flags & MVS_SWEEP_NO_RECT);
-        if (!rect && !generic && ctx->V > 0 && !ctx->fx_general_planned) {  // left out while the rectified kernel served the plan; before
-            ProfileScope pp(ctx, MVS_K_PLAN);                               // fill_params: it may (re)allocate the plan
-            if ((rc = sweep_fx_plan_general(ctx))) return rc;
-        }
-        SweepParams p;
-        fill_params(ctx, p, view_first, view_count, 8, 16);
-        p.debug = debug;
-        p.chunk0 = plane_first / 16;
-        p.chunk1 = div_up(plane_first + plane_count, 16);
-        p.ty0 = row_first / 8;
-        p.tyn = div_up(row_first + row_count, 8) - p.ty0;
-        p.row_begin = row_first;
-        p.row_end = min(ctx->H, row_first + row_count);
-        p.plane_begin = plane_first;
-        p.plane_end = min(ctx->D, plane_first + plane_count);
-        ProfileScope ps(ctx, MVS_K_SWEEP);
-        const int nsplit = rect ? sweep_rect_launch(ctx, p, vol, fused, flags) : sweep_fx_launch(ctx, p, vol, fused, generic, flags);
-        if (nsplit < 0) return nsplit;
-        if (p.part) {
-            const size_t first = (size_t)p.row_begin * ctx->W;
-            const size_t count = (size_t)(p.row_end - p.row_begin) * ctx->W;
-            combine_best<CS_FIXED><<<(unsigned)((count + 255) / 256), 256, 0, ctx->stream>>>(p, nsplit, first, count);
-            MVS_HIP(ctx, hipGetLastError());
-        }
-        return MVS_OK;
+    if (f.generic || ctx->V == 0) {
+        const dim3 grid(div_up(ctx->W, 64), div_up(p.row_end - p.row_begin, 4));
+        with_outputs(f.vol, f.fused, [&](auto vol, auto fused) {
+            sweep_generic<decltype(vol)::value, decltype(fused)::value><<<grid, 256, 0, ctx->stream>>>(p);
+        });
+    } else {
+        // padded group grid: 8 tiles per group, 8 groups per 64-id super block
+        const int groups = div_up(p.tiles_x, 2) * div_up(p.tyn, 4);
+        // plane split: aim at ~32 workgroups per CU (64 in round 1).  Finer work units smooth the tail of the launch and keep small
+        // frames / row bands from leaving CUs idle: c3 2.50 -> 2.31 ms, c2 0.414 -> 0.333 ms, c1 0.080 -> 0.055 ms,
+        // a 1/8 row band of c3 0.86 -> 0.4 ms; flat at c4 (8100 tiles) -- profiles/r01/exp_split.json
+        // round 2: 32 instead of 64 workgroups per CU (c3: 2 splits 1.92 ms, 4 splits 1.94)
+        int rc = choose_split(ctx, p, p.tiles_x * p.tyn, 32, f);
+        if (rc) return rc;
+        const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)split_count(p));
+        with_outputs(f.vol, f.fused, [&](auto vol, auto fused) {
+            constexpr bool VOL = decltype(vol)::value, FUSED = decltype(fused)::value;
+            if (p.pc == 32)
+                sweep_tiled<2, 32, VOL, FUSED><<<grid, 256, 0, ctx->stream>>>(p);
+            else
+                sweep_tiled<4, 16, VOL, FUSED><<<grid, 256, 0, ctx->stream>>>(p);
+        });
     }
+    MVS_HIP(ctx, hipGetLastError());
+    return MVS_OK;
+}
+
+static int sweep_run_fixed(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &f)
+{
+    if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "mvs_sweep_run: the fixed sampler's cells hold at most 255 views (have %d)", ctx->V);
+    // 1/256-texel coordinates live in the low 22 mantissa bits of a float in [2^23, 2^24): 256 * size + 132 must stay below 2^22
+    if (ctx->W > 16383 || ctx->H > 16383)
+        return fail(ctx, MVS_EINVAL, "mvs_sweep_run: the fixed sampler addresses images of up to 16383 x 16383 (have %d x %d); use MVS_SAMPLER_EXACT_F32",
+                    ctx->W, ctx->H);
+    int rc;
+    if (ctx->plan_valid && ctx->plan_shape != 3) ctx->plan_valid = false;
+    if (!f.generic && !ctx->plan_valid && ctx->V > 0) {
+        ProfileScope ps(ctx, MVS_K_PLAN);
+        if ((rc = sweep_fx_plan(ctx))) return rc;
+        ctx->plan_shape = 3;
+        ctx->plan_valid = true;
+    }
+    if (f.generic && (rc = ensure_pads(ctx))) return rc;  // the un-tiled kernel gathers single texels of the padded frames
+    // (a run over zero views writes empty cells: the general kernel's job -- the rectified one iterates over regions)
+    const bool rect = ctx->rect_ok && !f.generic && ctx->V > 0 && r.view_count > 0 && !f.no_rect;
+    if (!rect && !f.generic && ctx->V > 0 && !ctx->fx_general_planned) {  // left out while the rectified kernel served the plan; before
+        ProfileScope pp(ctx, MVS_K_PLAN);                                 // fill_params: it may (re)allocate the plan
+        if ((rc = sweep_fx_plan_general(ctx))) return rc;
+    }
+    SweepParams p;
+    fill_params(ctx, p, r.view_first, r.view_count, 8, 16);
+    p.debug = f.debug;
+    narrow_params(p, r.plane_first, r.plane_count, r.row_first, r.row_count);
+    ProfileScope ps(ctx, MVS_K_SWEEP);
+    if ((rc = rect ? sweep_rect_launch(ctx, p, f) : sweep_fx_launch(ctx, p, f))) return rc;
+    return merge_split_bests<CS_FIXED>(ctx, p);
+}
+
+static int sweep_run_exact(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &f)
+{
+    int rc;
     if (ctx->plan_valid && ctx->plan_shape == 3) ctx->plan_valid = false;  // the plan in memory belongs to the fixed sampler
-    if (!generic && (rc = ensure_quads16(ctx))) return rc;
+    if (!f.generic && (rc = ensure_quads16(ctx))) return rc;
 
     // Rectified views (the ring of SURVEY 8d) are served by sweep_exact_rect (sweep_xrect.hip); anything else, MVS_SWEEP_NO_RECT and the
     // forced 4 x 16 shape by sweep_tiled, whose region plan is made when it is first needed.
     // Thread shape of the tiled kernel (see the constants at the top): 2 pixels x 32 planes unless the planner finds
     // that more than 2 % of the regions a 32-plane chunk touches do not fit the LDS staging buffer
-    const bool force_tall = (debug & 8) != 0;
-    if (!generic && !ctx->plan_valid && ctx->V > 0) {
+    const bool force_tall = (f.debug & DBG_FORCE_4X16) != 0;
+    if (!f.generic && !ctx->plan_valid && ctx->V > 0) {
         ProfileScope ps(ctx, MVS_K_PLAN);
         if ((rc = sweep_xrect_plan(ctx))) return rc;
         ctx->exact_tiled_planned = false;
         ctx->plan_shape = 1;
         ctx->plan_valid = true;
     }
-    const bool xrect = ctx->xrect_ok && ctx->plan_valid && !generic && ctx->V > 0 && view_count > 0 && !force_tall && !(flags & MVS_SWEEP_NO_RECT);
+    const bool xrect = ctx->xrect_ok && ctx->plan_valid && !f.generic && ctx->V > 0 && r.view_count > 0 && !force_tall && !f.no_rect;
     if (xrect) {
         SweepParams p;
-        fill_params(ctx, p, view_first, view_count, 8, 16);
-        p.debug = debug;
-        p.chunk0 = plane_first / 16;
-        p.chunk1 = div_up(plane_first + plane_count, 16);
-        p.ty0 = row_first / 8;
-        p.tyn = div_up(row_first + row_count, 8) - p.ty0;
-        p.row_begin = row_first;
-        p.row_end = min(ctx->H, row_first + row_count);
+        fill_params(ctx, p, r.view_first, r.view_count, 8, 16);
+        p.debug = f.debug;
+        narrow_params(p, r.plane_first, r.plane_count, r.row_first, r.row_count);
         ProfileScope ps(ctx, MVS_K_SWEEP);
-        const int nsplit = sweep_xrect_launch(ctx, p, vol, fused, flags);
-        if (nsplit < 0) return nsplit;
-        if (p.part) {
-            const size_t first = (size_t)p.row_begin * ctx->W;
-            const size_t count = (size_t)(p.row_end - p.row_begin) * ctx->W;
-            combine_best<CS_EXACT><<<(unsigned)((count + 255) / 256), 256, 0, ctx->stream>>>(p, nsplit, first, count);
-            MVS_HIP(ctx, hipGetLastError());
-        }
+        if ((rc = sweep_xrect_launch(ctx, p, f))) return rc;
+        if ((rc = merge_split_bests<CS_EXACT>(ctx, p))) return rc;
         ctx->exact_last_shape = 5;
         return MVS_OK;
     }
     if ((rc = ensure_pads(ctx))) return rc;  // sweep_tiled's generic regions and the un-tiled kernel gather single texels of the padded frames
     if (ctx->exact_tiled_planned && ctx->plan_forced != force_tall) ctx->exact_tiled_planned = false;
-    if (!generic && !ctx->exact_tiled_planned && ctx->V > 0) {
+    if (!f.generic && !ctx->exact_tiled_planned && ctx->V > 0) {
         ctx->snap_valid = false;  // ctx->plan is about to hold the exact sampler's regions
         if ((rc = ensure(ctx, ctx->plan_stats, 64))) return rc;
         int *stats = (int *)ctx->plan_stats.ptr;
@@ -965,70 +961,42 @@ static int sweep_run_impl(mvs_ctx *ctx, int view_first, int view_count, int plan
         ctx->plan_forced = force_tall;
     }
     ctx->exact_last_shape = ctx->plan_shape;
-    const int shape = (generic || ctx->V == 0) ? 2 : ctx->plan_shape;
-    const int tile_h = shape == 1 ? 8 : 16, pc = shape == 1 ? 32 : 16;
+    const int shape = (f.generic || ctx->V == 0) ? 2 : ctx->plan_shape;
 
     SweepParams p;
-    fill_params(ctx, p, view_first, view_count, tile_h, pc);
-    p.debug = debug;
-    p.chunk0 = plane_first / pc;
-    p.chunk1 = div_up(plane_first + plane_count, pc);
-    p.ty0 = row_first / tile_h;
-    p.tyn = div_up(row_first + row_count, tile_h) - p.ty0;
-    p.row_begin = row_first;
-    p.row_end = min(ctx->H, row_first + row_count);
-    p.plane_begin = plane_first;
-    p.plane_end = min(ctx->D, plane_first + plane_count);
-    {
-        ProfileScope ps(ctx, MVS_K_SWEEP);
-        if (generic || ctx->V == 0) {
-            dim3 grid(div_up(ctx->W, 64), div_up(p.row_end - p.row_begin, 4));
-            if (vol && fused)
-                sweep_generic<true, true><<<grid, 256, 0, ctx->stream>>>(p);
-            else if (vol)
-                sweep_generic<true, false><<<grid, 256, 0, ctx->stream>>>(p);
-            else
-                sweep_generic<false, true><<<grid, 256, 0, ctx->stream>>>(p);
-        } else {
-            // padded group grid: 8 tiles per group, 8 groups per 64-id super block
-            const int groups = div_up(p.tiles_x, 2) * div_up(p.tyn, 4);
-            // plane split: aim at ~32 workgroups per CU (64 in round 1).  Finer work units smooth the tail of the launch and keep small
-            // frames / row bands from leaving CUs idle: c3 2.50 -> 2.31 ms, c2 0.414 -> 0.333 ms, c1 0.080 -> 0.055 ms,
-            // a 1/8 row band of c3 0.86 -> 0.4 ms; flat at c4 (8100 tiles) -- profiles/r01/exp_split.json
-            const int nch = p.chunk1 - p.chunk0, tiles = p.tiles_x * p.tyn;
-            int want = (int)((flags >> 16) & 0xffu);  // undocumented: forced split count for timing experiments
-            if (!want) want = div_up(32 * ctx->num_cus, tiles);  // round 2: 32 instead of 64 workgroups per CU (c3: 2 splits 1.92 ms, 4 splits 1.94)
-            p.cps = div_up(nch, max(1, min(want, nch)));
-            const int nsplit = div_up(nch, p.cps);
-            if (fused && nsplit > 1) {
-                if ((rc = ensure(ctx, ctx->best_parts, (size_t)nsplit * ctx->W * ctx->H * sizeof(uint2)))) return rc;
-                p.part = (uint2 *)ctx->best_parts.ptr;
-            }
-            const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)nsplit);
-            if (shape == 1) {
-                if (vol && fused)
-                    sweep_tiled<2, 32, true, true><<<grid, 256, 0, ctx->stream>>>(p);
-                else if (vol)
-                    sweep_tiled<2, 32, true, false><<<grid, 256, 0, ctx->stream>>>(p);
-                else
-                    sweep_tiled<2, 32, false, true><<<grid, 256, 0, ctx->stream>>>(p);
-            } else {
-                if (vol && fused)
-                    sweep_tiled<4, 16, true, true><<<grid, 256, 0, ctx->stream>>>(p);
-                else if (vol)
-                    sweep_tiled<4, 16, true, false><<<grid, 256, 0, ctx->stream>>>(p);
-                else
-                    sweep_tiled<4, 16, false, true><<<grid, 256, 0, ctx->stream>>>(p);
-            }
-            if (p.part) {
-                const size_t first = (size_t)p.row_begin * ctx->W;
-                const size_t count = (size_t)(p.row_end - p.row_begin) * ctx->W;
-                combine_best<CS_EXACT><<<(unsigned)((count + 255) / 256), 256, 0, ctx->stream>>>(p, nsplit, first, count);
-            }
-        }
-        MVS_HIP(ctx, hipGetLastError());
-    }
-    return MVS_OK;
+    fill_params(ctx, p, r.view_first, r.view_count, shape == 1 ? 8 : 16, shape == 1 ? 32 : 16);
+    p.debug = f.debug;
+    narrow_params(p, r.plane_first, r.plane_count, r.row_first, r.row_count);
+    ProfileScope ps(ctx, MVS_K_SWEEP);
+    if ((rc = sweep_tiled_launch(ctx, p, f))) return rc;
+    return merge_split_bests<CS_EXACT>(ctx, p);
+}
+
+static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags)
+{
+    if (!ctx) return MVS_EINVAL;
+    if (!ctx->have_main || !ctx->have_views || !ctx->have_planes)
+        return fail(ctx, MVS_ESTATE, "mvs_sweep_run: set main view, side views and planes first");
+    if (r.view_first < 0 || r.view_count < 0 || r.view_first + r.view_count > ctx->V)
+        return fail(ctx, MVS_EINVAL, "mvs_sweep_run: view range [%d,%d) outside 0..%d", r.view_first,
+                    r.view_first + r.view_count, ctx->V);
+    // Only the documented bits of `flags` reach the kernels.  Bits 8-23 carry timing-experiment switches (debug bits, forced plane-split
+    // count: tools/exp_*.py, tests) and are honoured only when the process sets MVS_DEBUG_FLAGS=1: a caller's stray high bits must not
+    // change tile order, look-ahead or split counts silently.
+    if (!ctx->hooks.debug_flags) flags &= (MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN | MVS_SWEEP_FORCE_GENERIC | MVS_SWEEP_NO_RECT);
+    SweepFlags f;
+    f.vol = (flags & MVS_SWEEP_VOLUME) != 0;
+    f.fused = (flags & MVS_SWEEP_FUSED_ARGMIN) != 0;
+    f.generic = (flags & MVS_SWEEP_FORCE_GENERIC) != 0;
+    f.no_rect = (flags & MVS_SWEEP_NO_RECT) != 0;
+    f.debug = (int)((flags >> 8) & 0xff);          // SweepDebug bits
+    f.forced_split = (int)((flags >> 16) & 0xff);  // forced split count for timing experiments
+    if (!f.vol && !f.fused) return fail(ctx, MVS_EINVAL, "mvs_sweep_run: flags select neither volume nor fused argmin");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_outputs(ctx, f.vol);
+    if (rc) return rc;
+    if (r.row_count <= 0 || r.plane_count <= 0) return MVS_OK;  // empty band or empty plane group: nothing to compute
+    return ctx->sampler == MVS_SAMPLER_FIXED ? sweep_run_fixed(ctx, r, f) : sweep_run_exact(ctx, r, f);
 }
 
 // depth selection over `vol` with the cell layout of the context's sampler; 16-byte loads when the pixel count and the pointer allow

@@ -512,7 +512,7 @@ __device__ __forceinline__ void sweep_fx_tiled_body(const SweepParams &p, const 
     uint2 *dtab = (uint2 *)(smem + FX_ROWS * FX_ROW_DW + FX_VB * 12);
     uint2 *best_state = (uint2 *)(smem + FX_ROWS * FX_ROW_DW + FX_VB * 14 + 2);  // (packed best cell, best index) per (pixel j, thread)
 
-    const int band_tile = (p.debug & 2) ? ((int)blockIdx.x < p.tiles_x * p.tyn ? (int)blockIdx.x : -1) : grouped_tile(blockIdx.x, p.tiles_x, p.tyn);
+    const int band_tile = (p.debug & DBG_LINEAR_TILES) ? ((int)blockIdx.x < p.tiles_x * p.tyn ? (int)blockIdx.x : -1) : grouped_tile(blockIdx.x, p.tiles_x, p.tyn);
     if (band_tile < 0) return;
     const int tx = band_tile % p.tiles_x, ty = band_tile / p.tiles_x + p.ty0;
     const int tile = ty * p.tiles_x + tx;
@@ -635,10 +635,10 @@ __device__ __forceinline__ void sweep_fx_tiled_body(const SweepParams &p, const 
             __syncthreads();  // this view's region has landed (the barrier drains vmcnt) and the previous one is no longer read
             // Request the next staged view's region into the other half of the rows, if both regions are at most FX_HALF_COL quads
             // wide: its copy (L2 / Infinity Cache latency, 1-2 us) then overlaps this view's sampling (0.5 us of work for the
-            // workgroup) and one barrier per region goes away.  Debug bit 3 switches it off (tests: bit-identical either way).
+            // workgroup) and one barrier per region goes away.  DBG_FX_NO_HALF_COL switches it off (tests: bit-identical either way).
             ahead = false;
             int nqcol = 0;
-            if (!(p.debug & 8) && rw <= FX_HALF_COL) {
+            if (!(p.debug & DBG_FX_NO_HALF_COL) && rw <= FX_HALF_COL) {
                 const unsigned mn = (unsigned)__builtin_amdgcn_readfirstlane((int)((dnext.y >> 16) & 7u));
                 const int rwn = __builtin_amdgcn_readfirstlane((int)(dnext.y & 0xffu));
                 if ((mn == FX_FAST || mn == FX_BORDER) && rwn <= FX_HALF_COL) {
@@ -652,7 +652,7 @@ __device__ __forceinline__ void sweep_fx_tiled_body(const SweepParams &p, const 
             const int kx0 = 256 * (x0 - qcol), ky0 = 256 * y0;  // region column rx sits in quad column qcol + rx of the LDS rows
             rg.offx = magic_plus(4 - kx0);
             rg.offy = magic_plus(4 - ky0);
-            const bool wconst = uniform_f(bw) == 0.0f && !(p.debug & 4);  // wave-uniform: plane-independent w
+            const bool wconst = uniform_f(bw) == 0.0f && !(p.debug & DBG_NO_CONST_W);  // wave-uniform: plane-independent w
             if (SEP && p.sep_y && mode == FX_FAST && uniform_f(q[1]) == 0.0f && uniform_f(q[4]) == 0.0f && uniform_f(q[8]) == 0.0f && uniform_f(q[9]) == 0.0f) {
                 // the separable path (above): this view has the main camera's orientation and the whole region is in frame
                 fast_views += 1u << 24;
@@ -870,20 +870,17 @@ int ensure_fx_lut(mvs_ctx *ctx)
     return MVS_OK;
 }
 
-// launch of the fixed-sampler sweep; `p` carries the plane / row / view ranges (sweep_run_impl in sweep.hip)
-int sweep_fx_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, bool generic, unsigned flags)
+// launch of the fixed-sampler sweep; `p` carries the plane / row / view ranges (sweep_run_fixed in sweep.hip)
+int sweep_fx_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f)
 {
     int rc = ensure_fx_lut(ctx);
     if (rc) return rc;
     const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
-    if (generic || ctx->V == 0) {
-        dim3 grid(div_up(ctx->W, 64), div_up(p.row_end - p.row_begin, 4));
-        if (vol && fused)
-            sweep_fx_generic<true, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
-        else if (vol)
-            sweep_fx_generic<true, false><<<grid, 256, 0, ctx->stream>>>(p, lut);
-        else
-            sweep_fx_generic<false, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
+    if (f.generic || ctx->V == 0) {
+        const dim3 grid(div_up(ctx->W, 64), div_up(p.row_end - p.row_begin, 4));
+        with_outputs(f.vol, f.fused, [&](auto vol, auto fused) {
+            sweep_fx_generic<decltype(vol)::value, decltype(fused)::value><<<grid, 256, 0, ctx->stream>>>(p, lut);
+        });
         MVS_HIP(ctx, hipGetLastError());
         return MVS_OK;
     }
@@ -893,31 +890,18 @@ int sweep_fx_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, bool gen
         p.sep_dpad = ctx->sep_dpad;
     }
     const int groups = div_up(p.tiles_x, 2) * div_up(p.tyn, 4);
-    const int nch = p.chunk1 - p.chunk0, tiles = p.tiles_x * p.tyn;
-    int want = (int)((flags >> 16) & 0xffu);  // undocumented: forced split count for timing experiments
-    if (!want) want = div_up(16 * ctx->num_cus, tiles);  // ~16 workgroups per CU (4 rounds of 4): c3 2 splits 1.44 ms (1: 1.46, 4: 1.46, 8: 1.50), c2 0.21 ms, c1 0.037 ms
-    p.cps = div_up(nch, max(1, min(want, nch)));
-    const int nsplit = div_up(nch, p.cps);
-    if (fused && nsplit > 1) {
-        if ((rc = ensure(ctx, ctx->best_parts, (size_t)nsplit * ctx->W * ctx->H * sizeof(uint2)))) return rc;
-        p.part = (uint2 *)ctx->best_parts.ptr;
-    }
-    const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)nsplit);
-    if (p.sep_y) {  // some view qualifies for the separable path: the instantiation that has it
-        if (vol && fused)
-            sweep_fx_tiled<true, true, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
-        else if (vol)
-            sweep_fx_tiled<true, false, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
+    // ~16 workgroups per CU (4 rounds of 4): c3 2 splits 1.44 ms (1: 1.46, 4: 1.46, 8: 1.50), c2 0.21 ms, c1 0.037 ms
+    if ((rc = choose_split(ctx, p, p.tiles_x * p.tyn, 16, f))) return rc;
+    const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)split_count(p));
+    with_outputs(f.vol, f.fused, [&](auto vol, auto fused) {
+        constexpr bool VOL = decltype(vol)::value, FUSED = decltype(fused)::value;
+        if (p.sep_y)  // some view qualifies for the separable path: the instantiation that has it
+            sweep_fx_tiled<VOL, FUSED, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
         else
-            sweep_fx_tiled<false, true, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
-    } else if (vol && fused)
-        sweep_fx_tiled<true, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
-    else if (vol)
-        sweep_fx_tiled<true, false><<<grid, 256, 0, ctx->stream>>>(p, lut);
-    else
-        sweep_fx_tiled<false, true><<<grid, 256, 0, ctx->stream>>>(p, lut);
+            sweep_fx_tiled<VOL, FUSED><<<grid, 256, 0, ctx->stream>>>(p, lut);
+    });
     MVS_HIP(ctx, hipGetLastError());
-    return nsplit;  // > 0: the caller merges the partial bests when p.part is set
+    return MVS_OK;
 }
 
 // The plan of the general tiled kernel (one descriptor per (tile, chunk, view)).  When every view is rectified the sweep runs on

@@ -1026,21 +1026,19 @@ int sweep_rect_plan(mvs_ctx *ctx, PlanHook *between)
 }
 
 template <int RS>
-static int launch_rect(mvs_ctx *ctx, const RectArgs &a, dim3 grid, size_t lds, bool vol, bool fused)
+static int launch_rect(mvs_ctx *ctx, const RectArgs &a, dim3 grid, size_t lds, const SweepFlags &f)
 {
-    auto go = [&](auto kernel) -> int {
+    return with_outputs(f.vol, f.fused, [&](auto vol, auto fused) -> int {
+        const auto kernel = sweep_fx_rect<RS, decltype(vol)::value, decltype(fused)::value>;
         MVS_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         kernel<<<grid, 256, lds, ctx->stream>>>(a);
         MVS_HIP(ctx, hipGetLastError());
         return MVS_OK;
-    };
-    if (vol && fused) return go(sweep_fx_rect<RS, true, true>);
-    if (vol) return go(sweep_fx_rect<RS, true, false>);
-    return go(sweep_fx_rect<RS, false, true>);
+    });
 }
 
-// launch of the rectified sweep; `p` carries the plane / row / view ranges.  Returns the split count like sweep_fx_launch.
-int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsigned flags)
+// launch of the rectified sweep; `p` carries the plane / row / view ranges
+int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f)
 {
     RectTables rt;
     rect_tables(ctx, p, rt);
@@ -1081,17 +1079,15 @@ int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsign
     a.tiles_x = p.tiles_x;
     a.slot_dw = ctx->rect_slot_dw;
     size_t lds = ((size_t)2 * a.slot_dw + RX_BIAS_X + (size_t)RX_BIAS_Y * ctx->rect_rs) * 4;  // two slots, the second one's data ends a bias further on
-    if (fused) lds = lds < 16384 ? 16384 : lds;  // the cross-wavefront depth selection borrows 16 KiB
+    if (f.fused) lds = lds < 16384 ? 16384 : lds;  // the cross-wavefront depth selection borrows 16 KiB
     if (lds > 160 * 1024) return fail(ctx, MVS_EINVAL, "sweep_rect_launch: %zu bytes of LDS", lds);
 
     const int groups = div_up(p.tiles_x, 2) * div_up(p.tyn, 4);
-    const int nch = p.chunk1 - p.chunk0, tiles = p.tiles_x * p.tyn;
-    int want = (int)((flags >> 16) & 0xffu);
-    if (!want) want = div_up(16 * ctx->num_cus, tiles);
-    p.cps = div_up(nch, max(1, min(want, nch)));
+    // (the buffer of the partial bests may be allocated here, ahead of the pack launch below: both are ordered on the stream)
+    int rc = choose_split(ctx, p, p.tiles_x * p.tyn, 16, f);
+    if (rc) return rc;
     a.cps = p.cps;
-    const int nsplit = div_up(nch, p.cps);
-    int rc;
+    a.part = p.part;
     // the records in the order this launch's workgroups walk them (plan_rect_pack); kept until a launch asks for another
     const std::array<int, 5> order = {p.v0, p.vcount, p.chunk0, p.chunk1, p.cps};
     if (order != ctx->rect_order) {
@@ -1100,16 +1096,9 @@ int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsign
         MVS_HIP(ctx, hipGetLastError());
         ctx->rect_order = order;
     }
-    if (fused && nsplit > 1) {
-        if ((rc = ensure(ctx, ctx->best_parts, (size_t)nsplit * ctx->W * ctx->H * sizeof(uint2)))) return rc;
-        p.part = (uint2 *)ctx->best_parts.ptr;
-        a.part = p.part;
-    }
-    const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)nsplit);
-    rc = ctx->rect_rs == 64 ? launch_rect<64>(ctx, a, grid, lds, vol, fused) : ctx->rect_rs == 84 ? launch_rect<84>(ctx, a, grid, lds, vol, fused)
-       : ctx->rect_rs == 96 ? launch_rect<96>(ctx, a, grid, lds, vol, fused) : launch_rect<128>(ctx, a, grid, lds, vol, fused);
-    if (rc) return rc;
-    return nsplit;
+    const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)split_count(p));
+    return ctx->rect_rs == 64 ? launch_rect<64>(ctx, a, grid, lds, f) : ctx->rect_rs == 84 ? launch_rect<84>(ctx, a, grid, lds, f)
+         : ctx->rect_rs == 96 ? launch_rect<96>(ctx, a, grid, lds, f) : launch_rect<128>(ctx, a, grid, lds, f);
 }
 
 }  // namespace mvs

@@ -5,6 +5,9 @@
 #pragma once
 #include "mvs_internal.hpp"
 
+#include <climits>
+#include <type_traits>
+
 namespace mvs {
 
 constexpr int CS_EXACT = 16, CS_FIXED = 24;
@@ -15,7 +18,7 @@ constexpr int TILE_W = 64;   // one wavefront spans a tile row
 // sweep_tiled is instantiated for two thread shapes with 64 accumulators each (NPX pixels x PC planes per thread, tile
 // height 4 * NPX): 2 x 32 amortises the per-(pixel, view) set-up and the staged texels over twice as many planes
 // (c3: 2.20 -> 2.09 ms) but needs the warped footprint of 32 consecutive planes to fit the LDS region; 4 x 16 is the
-// fallback when the planner reports oversize regions (wide baselines with few planes).  Chosen per plan, see sweep_run_impl.
+// fallback when the planner reports oversize regions (wide baselines with few planes).  Chosen per plan, see sweep_run_exact.
 constexpr int PCG = 16;          // planes per accumulator batch of the un-tiled generic kernel
 constexpr int ROW_GRAN = 16;     // public row granularity: a multiple of both tile heights
 constexpr int PLANE_GRAN = 32;   // public plane granularity: a multiple of both chunk sizes
@@ -24,6 +27,25 @@ constexpr int MAX_RW = 192;
 constexpr float PLAN_MARGIN = 0.0625f;
 
 enum RegionMode : unsigned { R_SKIP = 0, R_FAST = 1, R_BORDER = 2, R_GENERIC = 3 };
+
+// The timing-experiment switches: bits 8-15 of mvs_sweep_run's flags, honoured only under MVS_DEBUG_FLAGS=1 (sweep_run_impl) and handed to
+// the kernels in SweepParams::debug.  Tests and tools pass them as numbers, so the values stay.  Results are bit-identical with any of
+// them set, DBG_NO_STAGING excepted.
+enum SweepDebug : int {
+    DBG_NO_STAGING = 1,       // sweep_tiled: skip the LDS staging of the side regions (wrong results; times everything else)
+    DBG_LINEAR_TILES = 2,     // sweep_tiled, sweep_fx_tiled: block id = tile id instead of the XCD-aware grouped order
+    DBG_NO_CONST_W = 4,       // sweep_tiled, sweep_fx_tiled: never take the plane-independent-w path
+    DBG_FORCE_4X16 = 8,       // exact sampler, host side: sweep_tiled in its 4 x 16 shape, never 2 x 32 or sweep_exact_rect
+    DBG_FX_NO_HALF_COL = 8,   // the same bit in sweep_fx_tiled: no half-column path (the next region is not staged ahead)
+    DBG_NO_PAIRED_READS = 16  // sweep_tiled<2, 32>: general cameras take the plain sample loop, not the hand-pipelined one
+};
+
+// mvs_sweep_run's `flags`, decoded once by sweep_run_impl
+struct SweepFlags {
+    bool vol, fused, generic, no_rect;  // MVS_SWEEP_VOLUME, _FUSED_ARGMIN, _FORCE_GENERIC, _NO_RECT
+    int debug;                          // SweepDebug bits
+    int forced_split;                   // plane-split count forced by a timing experiment; 0: the launcher's target decides
+};
 
 struct SweepParams {
     const uint8_t *__restrict__ main_img;
@@ -58,7 +80,7 @@ struct SweepParams {
     const float *__restrict__ sep_r;   // [V][sep_dpad]
     const uint2 *__restrict__ sep_y;   // [V][H][sep_dpad]: (ky << 10, iy << 10)
     int sep_dpad, sep_reserved;
-    int debug;  // timing experiments only (bit 0: skip LDS staging -> wrong results; bit 1: linear tile order; bit 2: never use the plane-independent-w path; bit 3: exact sampler: force the 4 x 16 shape, fixed sampler: no region look-ahead; fixed sampler only: bit 4: BORDER regions as FAST, bit 5: skip the sample loop)
+    int debug;  // timing experiments only: SweepDebug bits
 };
 
 // ------------------------------------------------------------------------------------------------------
@@ -209,6 +231,58 @@ inline int fill_params(mvs_ctx *ctx, SweepParams &p, int v0, int vcount, int til
     return MVS_OK;
 }
 
+// host: narrows filled parameters to planes [plane_first, +plane_count) and rows [row_first, +row_count), in the units of the shape
+// they were filled for (p.pc planes per chunk, tiles of p.tile_h rows) and in planes / pixels
+inline void narrow_params(SweepParams &p, int plane_first, int plane_count, int row_first, int row_count)
+{
+    p.chunk0 = plane_first / p.pc;
+    p.chunk1 = div_up(plane_first + plane_count, p.pc);
+    p.ty0 = row_first / p.tile_h;
+    p.tyn = div_up(row_first + row_count, p.tile_h) - p.ty0;
+    p.row_begin = row_first;
+    p.row_end = min(p.H, row_first + row_count);
+    p.plane_begin = plane_first;
+    p.plane_end = min(p.D, plane_first + plane_count);
+}
+
+// host: plane splits of a launch = gridDim.y
+inline int split_count(const SweepParams &p) { return div_up(p.chunk1 - p.chunk0, p.cps); }
+
+// host: the plane split of a tiled launch whose ranges are set.  A launch with too few tiles to fill the chip hands each workgroup
+// p.cps of a tile's plane chunks (blockIdx.y selects them), aiming at `wgs_per_cu` workgroups per CU unless an experiment forces the
+// split count; `max_cps` bounds what one workgroup can take.  With a fused depth selection the splits' partial bests go to p.part,
+// for merge_split_bests (sweep.hip).
+inline int choose_split(mvs_ctx *ctx, SweepParams &p, int tiles, int wgs_per_cu, const SweepFlags &f, int max_cps = INT_MAX)
+{
+    const int nch = p.chunk1 - p.chunk0;
+    const int want = f.forced_split ? f.forced_split : div_up(wgs_per_cu * ctx->num_cus, tiles);
+    p.cps = max(1, min(div_up(nch, max(1, min(want, nch))), max_cps));
+    if (f.fused && split_count(p) > 1) {
+        int rc = ensure(ctx, ctx->best_parts, (size_t)split_count(p) * p.W * p.H * sizeof(uint2));
+        if (rc) return rc;
+        p.part = (uint2 *)ctx->best_parts.ptr;
+    }
+    return MVS_OK;
+}
+
+// host: calls f(std::bool_constant<VOL>, std::bool_constant<FUSED>) for the outputs a launch writes, so that a launcher names its kernel
+// once.  Neither output is rejected by sweep_run_impl and is never instantiated.
+template <class F>
+inline auto with_outputs(bool vol, bool fused, F &&f)
+{
+    if (vol && fused) return f(std::true_type{}, std::true_type{});
+    if (vol) return f(std::true_type{}, std::false_type{});
+    return f(std::false_type{}, std::true_type{});
+}
+
+// the launchers: `p` carries the view / plane / row ranges; each chooses its plane split; the caller merges the partial bests
+// (merge_split_bests in sweep.hip)
+int sweep_fx_plan_general(mvs_ctx *ctx);                                    // sweep_fx.hip: the fixed-point sampler (contract v2)
+int sweep_fx_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f);
+int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f);   // sweep_rect.hip: the fixed sampler on rectified views
+int sweep_xrect_plan(mvs_ctx *ctx);                                         // sweep_xrect.hip: the exact sampler on rectified views
+int sweep_xrect_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f);
+int warp_by_depth_fx_launch(mvs_ctx *ctx, const float *depth_dev, const float *q_dev, const uint8_t *pad_dev, int pitch, uint8_t *out2_dev);
 
 
 // Planner counters: every thread of a launch used to hit the same two or three addresses with an atomic (0.2-0.3 ms of serialised L2

@@ -581,39 +581,28 @@ int sweep_xrect_plan(mvs_ctx *ctx)
     return MVS_OK;
 }
 
-// launch of the rectified exact-sampler sweep; `p` carries the plane / row / view ranges.  Returns the split count like sweep_fx_launch.
-int sweep_xrect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsigned flags)
+// launch of the rectified exact-sampler sweep; `p` carries the plane / row / view ranges
+int sweep_xrect_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f)
 {
     XrArgs a;
     fill_args(ctx, p, a);
     const int groups = div_up(a.tiles_x, 2) * div_up(p.tyn, 4);
-    const int nch = p.chunk1 - p.chunk0, tiles = a.tiles_x * p.tyn;
-    int want = (int)((flags >> 16) & 0xffu);
-    if (!want) want = div_up(16 * ctx->num_cus, tiles);
-    p.cps = div_up(nch, max(1, min(want, nch)));
-    p.cps = max(1, min(p.cps, XR_MAX_REGIONS / max(1, p.vcount)));  // the records of a workgroup's regions live in LDS (64 bytes each)
-    size_t lds = 2 * (size_t)a.slot_bytes + 64 * (size_t)p.cps * (size_t)max(1, p.vcount) + 128;  // slots, records, 32 bytes per wavefront for the row fractions
-    if (fused) lds = lds < 16384 ? 16384 : lds;  // the cross-wavefront depth selection borrows 16 KiB
+    // ~16 workgroups per CU; the records of a workgroup's regions live in LDS (64 bytes each), which bounds its chunks
+    int rc = choose_split(ctx, p, a.tiles_x * p.tyn, 16, f, XR_MAX_REGIONS / max(1, p.vcount));
+    if (rc) return rc;
     a.cps = p.cps;
-    const int nsplit = div_up(nch, p.cps);
-    int rc;
-    if (fused && nsplit > 1) {
-        if ((rc = ensure(ctx, ctx->best_parts, (size_t)nsplit * ctx->W * ctx->H * sizeof(uint2)))) return rc;
-        p.part = (uint2 *)ctx->best_parts.ptr;
-        a.part = p.part;
-    }
-    const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)nsplit);
-    auto go = [&](auto kernel) -> int {
-        MVS_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        kernel<<<grid, 256, lds, ctx->stream>>>(a);
-        MVS_HIP(ctx, hipGetLastError());
-        return MVS_OK;
-    };
+    a.part = p.part;
+    size_t lds = 2 * (size_t)a.slot_bytes + 64 * (size_t)p.cps * (size_t)max(1, p.vcount) + 128;  // slots, records, 32 bytes per wavefront for the row fractions
+    if (f.fused) lds = lds < 16384 ? 16384 : lds;  // the cross-wavefront depth selection borrows 16 KiB
+    const dim3 grid((unsigned)(div_up(groups, 8) * 64), (unsigned)split_count(p));
     auto pick = [&](auto rs_tag) -> int {
-        constexpr int RS = decltype(rs_tag)::value;
-        if (vol && fused) return go(sweep_exact_rect<true, true, RS>);
-        if (vol) return go(sweep_exact_rect<true, false, RS>);
-        return go(sweep_exact_rect<false, true, RS>);
+        return with_outputs(f.vol, f.fused, [&](auto vol, auto fused) -> int {
+            const auto kernel = sweep_exact_rect<decltype(vol)::value, decltype(fused)::value, decltype(rs_tag)::value>;
+            MVS_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            kernel<<<grid, 256, lds, ctx->stream>>>(a);
+            MVS_HIP(ctx, hipGetLastError());
+            return MVS_OK;
+        });
     };
     switch (a.rs) {
     case 72: rc = pick(std::integral_constant<int, 72>{}); break;
@@ -623,8 +612,7 @@ int sweep_xrect_launch(mvs_ctx *ctx, SweepParams &p, bool vol, bool fused, unsig
     case 128: rc = pick(std::integral_constant<int, 128>{}); break;
     default: rc = pick(std::integral_constant<int, 0>{}); break;
     }
-    if (rc) return rc;
-    return nsplit;
+    return rc;
 }
 
 }  // namespace mvs

@@ -360,7 +360,9 @@ def test_plane_groups_reproduce_the_full_volume(sampler):
         ctx.sweep_run(0, V, mvs_amd.MVS_SWEEP_VOLUME)
         ctx.sweep_argmin()
         d_full, c_full, i_full, v_full = [a.copy() for a in ctx.sweep_fetch(want_volume=True)]
-        for kernel_flag in (0, mvs_amd.MVS_SWEEP_FORCE_GENERIC):
+        # the ring is rectified: 0 takes the rectified kernels, NO_RECT the general tiled ones, 8 << 8 the exact sampler's 4 x 16 shape
+        routes = (0, mvs_amd.MVS_SWEEP_FORCE_GENERIC, mvs_amd.MVS_SWEEP_NO_RECT) + ((8 << 8,) if sampler == "exact" else ())
+        for kernel_flag in routes:
             # poison the volume, then rebuild it group by group
             ctx.sweep_run(0, 0, mvs_amd.MVS_SWEEP_VOLUME | kernel_flag)
             for first, count in mdist.plane_groups(D, 3, ctx.plane_granularity()):
@@ -426,7 +428,12 @@ def test_row_bands_reproduce_the_full_result(sampler):
         ctx.sweep_set(main_cam, main_img, side_cams, sides, D)
         ctx.sweep_run(0, V, both)
         d_full, c_full, i_full, v_full = [a.copy() for a in ctx.sweep_fetch(want_volume=True)]
-        for kernel_flag in (0, mvs_amd.MVS_SWEEP_FORCE_GENERIC):
+        # the ring is rectified: 0 takes the rectified kernels, NO_RECT the general tiled ones, 8 << 8 the exact sampler's 4 x 16 shape;
+        # 3 << 16 forces 3 plane splits where D = 24 has 2 chunks of 16 planes or 1 of 32: the count is clamped and the partial bests
+        # are merged over bands that do not start at row 0
+        routes = (0, mvs_amd.MVS_SWEEP_FORCE_GENERIC, mvs_amd.MVS_SWEEP_NO_RECT) + ((8 << 8,) if sampler == "exact" else ())
+        routes += (3 << 16, mvs_amd.MVS_SWEEP_NO_RECT | (3 << 16))
+        for kernel_flag in routes:
             for world in (2, 3, 5):
                 ctx.sweep_run(0, 0, both | kernel_flag)          # poison: zero views -> empty cells, depth 1.0
                 assert (ctx.sweep_fetch()[0] == 1.0).all()
