@@ -233,6 +233,34 @@ int mvs_sweep_refine_depth(mvs_ctx *ctx);
 int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, unsigned flags);
 void *mvs_sweep_aggregated_device(mvs_ctx *ctx, size_t *bytes);
 int mvs_sweep_aggregate_fetch(mvs_ctx *ctx, uint16_t *s_dhw);
+/* Cleaning of the selected depth / cost / index maps before they vote into a fusion (DESIGN.md section 16 is the contract; integer
+ * arithmetic, bit-identical to tests/clean_mirror.py).  A rejected pixel gets index -1, MVS_BACKGROUND_DEPTH, +inf -- what everything
+ * downstream already reads as "empty" -- and every other pixel keeps its three values bit for bit, a refined depth included (so call it
+ * after mvs_sweep_refine_depth or MVS_AGGREGATE_REFINE).  With cell = packed volume cell of the pixel's selected plane i, n its count:
+ *   rule 1, view count (min_views 0..255; 0 and 1 reject nothing the library selected): rejected when n(i) < min_views;
+ *   rule 2, uniqueness (uniqueness_percent u 0..99; 0 = off): of the pixels rule 1 kept, rejected when some plane d that a view sees with
+ *     |d - i| >= 2 has score(d) (100 - u) < score(i) 100 (StereoSGBM's uniquenessRatio); the score is the cell's mean cost compared as an
+ *     exact rational, s_d n_i (100 - u) < s_i n_d 100 in 64 bits, or with MVS_CLEAN_SCORES_AGGREGATED the sum S of the last
+ *     mvs_sweep_aggregate;
+ *   rule 3, speckle (speckle_min_size 0 = off; speckle_max_diff 0..255 planes): on the index map rules 1-2 left, 4-neighbours are
+ *     connected when both have an index and the indices differ by at most speckle_max_diff; a pixel whose connected component
+ *     (transitive closure) has fewer than speckle_min_size pixels is rejected.  All sizes are computed before any pixel is rewritten;
+ *     the size map (0 for a pixel without an index) stays on the device for mvs_sweep_clean_sizes_*.
+ * Rules 1 and 2 are evaluated on the incoming maps; a pixel that fails rule 1 is counted under rule 1 only.  Asynchronous on the
+ * context's stream, like mvs_sweep_argmin, and timed under MVS_K_ARGMIN; the number of launches does not depend on the maps.  Neither the
+ * packed volume nor S is modified: mvs_sweep_argmin or mvs_sweep_aggregate afterwards restores the uncleaned maps.  Cleaning twice with
+ * the same parameters rejects nothing the second time.  mvs_sweep_clean_report synchronises: pixels with an index before the call, and
+ * pixels rejected by rule 1, 2, 3.
+ * Errors: MVS_EINVAL for a NULL ctx or array, a parameter outside its range, unknown flag bits; MVS_ESTATE without a depth selection,
+ * for min_views >= 2 or uniqueness_percent > 0 without a packed volume of nplanes * H * W cells (min_views 1 is tested where the context has
+ * one), for MVS_CLEAN_SCORES_AGGREGATED without an S of the current plane count, for mvs_sweep_clean_report before the first clean and
+ * for mvs_sweep_clean_sizes_fetch unless the last clean ran rule 3 (mvs_sweep_clean_sizes_device: NULL then); MVS_ENOMEM.  After an error
+ * the maps are untouched.  Speckle-only cleaning needs no volume (it works after an MVS_SWEEP_FUSED_ARGMIN run). */
+#define MVS_CLEAN_SCORES_AGGREGATED 1u
+int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int speckle_min_size, int speckle_max_diff, unsigned flags);
+int mvs_sweep_clean_report(mvs_ctx *ctx, int out[4]);
+void *mvs_sweep_clean_sizes_device(mvs_ctx *ctx);
+int mvs_sweep_clean_sizes_fetch(mvs_ctx *ctx, int32_t *sizes_hw);
 /* The same selection in two steps, for a view-sharded job that REDUCE-SCATTERS the packed volume instead of all-reducing it
  * (half the bytes over xGMI): rank r owns the summed cells of planes [plane_first, plane_first + plane_count) in
  * `volume_slice_dev` ([plane_count][H][W] u32) and selects a partial best per pixel over them -- `partial_out_dev` receives

@@ -182,6 +182,11 @@ struct mvs_ctx {
     // agg_planes = D of the last call (0: nothing aggregated yet)
     mvs::DevBuf agg_cost, agg_sum;
     int agg_planes = 0;
+    // cleaning of the selected maps (clean.hip: mvs_sweep_clean): H*W i32 labels followed by H*W i32 roots, the H*W i32 component sizes
+    // (valid while clean_have_sizes: the last clean ran the speckle filter) and the report's four counters (valid once clean_done).
+    // Allocated by the first call that needs them.
+    mvs::DevBuf clean_labels, clean_sizes, clean_counters;
+    bool clean_done = false, clean_have_sizes = false;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

@@ -22,6 +22,7 @@ MVS_SWEEP_FUSED_ARGMIN = 2
 MVS_SWEEP_FORCE_GENERIC = 4
 MVS_SWEEP_NO_RECT = 8
 MVS_AGGREGATE_REFINE = 1
+MVS_CLEAN_SCORES_AGGREGATED = 1
 MVS_SHARD_ROWS, MVS_SHARD_VIEWS, MVS_SHARD_VIEWS_SCATTER = 0, 1, 2
 SHARD_MODES = {"rows": 0, "views": 1, "views_scatter": 2}
 MVS_SAMPLER_FIXED, MVS_SAMPLER_EXACT_F32 = 0, 1
@@ -109,6 +110,10 @@ ABI = [
     ("mvs_sweep_aggregate", _i, [_vp, _i, _i, _i, _i, C.c_uint]),
     ("mvs_sweep_aggregated_device", _vp, [_vp, C.POINTER(_sz)]),
     ("mvs_sweep_aggregate_fetch", _i, [_vp, C.POINTER(C.c_uint16)]),
+    ("mvs_sweep_clean", _i, [_vp, _i, _i, _i, _i, C.c_uint]),
+    ("mvs_sweep_clean_report", _i, [_vp, C.POINTER(_i)]),
+    ("mvs_sweep_clean_sizes_device", _vp, [_vp]),
+    ("mvs_sweep_clean_sizes_fetch", _i, [_vp, _i32p]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
     ("mvs_sweep_combine_partials", _i, [_vp, _vp, _i]),
     ("mvs_sweep_volume_device", _vp, [_vp, C.POINTER(_sz)]),
@@ -957,6 +962,24 @@ class Context:
         if not p:
             raise MvsError("nothing aggregated yet (sweep_aggregate first)")
         return p, n.value
+
+    def sweep_clean(self, min_views=0, uniqueness=0, speckle_min_size=0, speckle_max_diff=1, aggregated=False):
+        """mvs_sweep_clean: reject pixels of the depth / cost / index maps by view count, uniqueness (in per cent; `aggregated`: on the
+        sums of the last sweep_aggregate) and component size (asynchronous, stream-ordered)"""
+        self._check(self.lib.mvs_sweep_clean(self.h, int(min_views), int(uniqueness), int(speckle_min_size), int(speckle_max_diff),
+                                             MVS_CLEAN_SCORES_AGGREGATED if aggregated else 0))
+
+    def sweep_clean_report(self):
+        """mvs_sweep_clean_report -> [pixels with an index before the last sweep_clean, rejected by rule 1, 2, 3] (synchronises)"""
+        out = (C.c_int * 4)()
+        self._check(self.lib.mvs_sweep_clean_report(self.h, out))
+        return list(out)
+
+    def sweep_clean_sizes(self):
+        """mvs_sweep_clean_sizes_fetch -> (H, W) int32 component sizes of the last sweep_clean's speckle filter (synchronises)"""
+        sizes = np.empty((self.H, self.W), np.int32)
+        self._check(self.lib.mvs_sweep_clean_sizes_fetch(self.h, _ptr(sizes, _i32p)))
+        return sizes
 
     def sweep_argmin_partial(self, volume_slice_ptr, plane_first, plane_count, partial_out_ptr):
         self._check(self.lib.mvs_sweep_argmin_partial(self.h, C.c_void_p(volume_slice_ptr), int(plane_first), int(plane_count),
