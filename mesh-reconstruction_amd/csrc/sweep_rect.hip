@@ -36,6 +36,10 @@
 // the current plane's arithmetic; otherwise one statement per plane (M0-based ds_read_addtid_b32, v_dot4_u32_u8, v_sad_u16; border
 // planes under EXEC masks, planes with nothing in frame branched over) plus the block for failed certificates.  Not compiler code: the
 // compiler would order every ds_read behind ALL pending LDS copies.
+// The chunk epilogue (the 32 cost volume stores of a wavefront and its depth selection over its four planes) does not run where the
+// chunk's last view has been sampled -- the next instruction there is the full wait, and stores count in vmcnt like the copies -- but
+// one turn later, behind the barrier and the issue of the next copy and in front of the sampling: the write acknowledgements then
+// have a region's sampling to come back in.  The workgroup's last chunk is finished behind the loop.
 // What bounds it (profiles/r03): vector-instruction issue.  Measured and rejected: a second region of look-ahead
 // with counted waits (three slots, records through an LDS ring; +10 %), row-wise copies (+8 %), copies that all hit in L2 (no change).
 #include "sweep_shared.hpp"
@@ -435,7 +439,7 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
 
     // copy instructions of this wavefront per region: a constant of the launch (the slot holds a.slot_dw / 256 instructions' worth;
     // one more would land in the other slot)
-    const int ni_wave = (a.slot_dw / 256 + 3 - wave) >> 2;
+    int ni_wave = (a.slot_dw / 256 + 3 - wave) >> 2;
 
     const int chunk_first = a.chunk0 + (int)blockIdx.y * a.cps;
     const int chunk_last = min(a.chunk1, chunk_first + a.cps);
@@ -453,16 +457,17 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
     // fetched).  Every wavefront issues all its instructions for every region, whole wavefront, no EXEC write: a lane past the box's
     // last row fetches nothing (the slot has room for it: a.slot_dw counts whole instructions, and no read goes there).
     typedef __attribute__((address_space(3))) char *lds_ptr;
-    const uint32_t wdst = lds_base + 4u * (uint32_t)(SLOT_BIAS_DW + wave * 256);
-    auto issue_copy = [&](uint32_t src, uint32_t end, uint32_t slot_b) {
+    const uint32_t wrel = 4u * (uint32_t)(SLOT_BIAS_DW + wave * 256);  // where this wavefront's first instruction lands inside a slot
+    auto issue_copy = [&](uint32_t src, uint32_t end, uint32_t dst_b) {
         const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void *)a.quads, 0, (int)end, 0x00020000);
-        const lds_ptr dst = (lds_ptr)(uintptr_t)(wdst + slot_b);
+        const lds_ptr dst = (lds_ptr)(uintptr_t)dst_b;
         static_assert(RX_MAX_NI == 3, "the three lines below");
-        int ni = ni_wave;
-        asm volatile("" : "+s"(ni));  // (compared where it is used, s_cmp + s_cbranch_scc: or the tests live in SGPR pairs over the whole loop)
-        if (ni >= 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst, 16, srcoff[0], src, 0, 0);
-        if (ni >= 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst + 4096, 16, srcoff[1], src, 0, 0);
-        if (ni >= 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst + 8192, 16, srcoff[2], src, 0, 0);
+        // (compared where it is used, s_cmp + s_cbranch_scc: or the tests live in SGPR pairs over the whole loop.  The count itself goes
+        // through the statement, not a copy of it: one register for the whole loop and no s_mov per turn)
+        asm volatile("" : "+s"(ni_wave));
+        if (ni_wave >= 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst, 16, srcoff[0], src, 0, 0);
+        if (ni_wave >= 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst + 4096, 16, srcoff[1], src, 0, 0);
+        if (ni_wave >= 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(rq, dst + 8192, 16, srcoff[2], src, 0, 0);
     };
 
     // The records travel through VECTOR registers (lane l holds dword l; one v_readlane per scalar when the region's turn comes): as
@@ -487,17 +492,86 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
     uint32_t spacc = 0u;  // per plane of this wavefront (one byte each): views of the current chunk whose plane was NOT counted as a whole
 
     // prologue: the record of region 0 and, from its own fields, the copy of region 0
-    uint32_t xl = load_rec(xo), yl = load_rec(xo + ydelta);
+    uint32_t yo = xo + ydelta;  // (an offset of its own, stepped like xo: no add between the barrier and the second load)
+    uint32_t xl = load_rec(xo), yl = load_rec(yo);
     xo += 4u * 4u * RX_REC;
-    const uint32_t slot_bytes = 4u * (uint32_t)a.slot_dw;
-    uint32_t slot_cur = 0u;  // LDS byte offset of the slot being sampled: 0 or slot_bytes
+    yo += 4u * 4u * RX_REC;
+    // LDS byte address of the slot being sampled.  The two slots' addresses add up to slot_flip, so the other slot is one subtraction
+    // away, and so is where this wavefront's copy into the other slot lands (copy_flip): nothing else is derived per turn.
+    const uint32_t slot_flip = 2u * lds_base + 4u * (uint32_t)a.slot_dw, copy_flip = slot_flip + wrel;
+    uint32_t slot_cur = lds_base;
     asm volatile("" : "+s"(slot_cur));  // (a scalar from the start: sharing the accumulators' zero would take it, and every M0 after it, through vector registers)
     if (nreg > 0) {
         const uint32_t xsx = rdl(xl, 13), rows = (xsx >> 16) ? rdl(yl, 14) & 0xffu : 0u;
         const uint32_t src = (xsx & 0xffffu) + rdl(yl, 15);
-        issue_copy(src, rows ? src + 4u * ((rows - 1u) * (uint32_t)a.pitch + (uint32_t)RS) : 0u, slot_cur);
+        issue_copy(src, rows ? src + 4u * ((rows - 1u) * (uint32_t)a.pitch + (uint32_t)RS) : 0u, slot_cur + wrel);
     }
-    int chunk = chunk_first, vleft = a.vcount;  // views of the chunk still to come, this one included
+    int chunk = chunk_first, vleft = a.vcount;  // views of the chunk still to come, this one included; 0: the chunk's epilogue is pending
+
+    // ---- chunk epilogue ---- (cost volume stores and this wavefront's depth selection over the chunk's four planes of its own)
+    // It does NOT run at the end of the turn of the chunk's last view: the stores count in vmcnt like the copies, and the next thing
+    // every wavefront does there is wait for vmcnt(0) and the barrier -- 32 write acknowledgements per wavefront with nothing to cover
+    // them.  It runs one turn later (vleft == 0 says it is pending), behind the barrier and behind the issue of the next copy, in front
+    // of that turn's sampling: the stores then have a whole region's sampling before the next full wait.  The workgroup's last chunk
+    // is finished behind the loop.  A macro, not a lambda: through a closure two of bi[] end up in scratch memory.
+    //  * W, H: not loop-invariant for the optimiser -- what is derived from them (the rows' offsets, the row tests of a ragged tile in
+    //    SGPR pairs) is derived here, once per chunk, not held in SGPRs over the whole region loop.
+    //  * pix0: byte offset of this lane's first pixel inside a plane.
+    //  * While every plane of every chunk so far was FULL for every view, every cell carries the same count and the packed cells
+    //    compare like their sums: "cell < best" (best starts at 0xffffffff) instead of the cross-multiplied comparison.  The first
+    //    chunk with a plane that is not FULL ends that for the rest of the workgroup (same packed cells, start value 1).
+    //  * cntk: FULL planes -- every cell gets the view's count.  One buffer resource per plane (a volume can exceed the 4 GiB a
+    //    resource spans), rows by the wave-uniform offset; nt stores: written once, read by a later kernel.
+#define RX_CHUNK_EPILOGUE                                                                                                                                                    \
+    int W = a.W, H = a.H;                                                                                                                                                    \
+    asm volatile("" : "+s"(W), "+s"(H));                                                                                                                                     \
+    const int d0 = chunk * RX_PC + wave * RX_KW;                                                                                                                             \
+    const size_t P = (size_t)W * H;                                                                                                                                          \
+    const uint32_t pix0 = 4u * (uint32_t)(row0 * W + col);                                                                                                                   \
+    const int nrows = min(8, H - row0);                                                                                                                                      \
+    if (FUSED && plain && spacc != 0u) {                                                                                                                                     \
+        plain = false;                                                                                                                                                       \
+    _Pragma("unroll")                                                                                                                                                        \
+        for (int j = 0; j < 8; j++) best[j] = bi[j] < 0 ? 1u : best[j];                                                                                                      \
+    }                                                                                                                                                                        \
+    auto finish = [&](auto checked_rows, auto plain_compare) {                                                                                                               \
+    _Pragma("unroll")                                                                                                                                                        \
+        for (int k = 0; k < RX_KW; k++) {                                                                                                                                    \
+            const uint32_t cntk = ((uint32_t)a.vcount - ((spacc >> (8 * k)) & 0xffu)) << 24;                                                                                 \
+            if (d0 + k < a.D) {                                                                                                                                              \
+                const __amdgpu_buffer_rsrc_t rvol = make_rsrc(WRITE_VOLUME ? a.volume + (size_t)(d0 + k) * P : nullptr, 0xffffffffu);                                        \
+    _Pragma("unroll")                                                                                                                                                        \
+                for (int j = 0; j < 8; j++) {                                                                                                                                \
+                    if (!checked_rows.value || j < nrows) {                                                                                                                  \
+                        const uint32_t cell = acc[j][k] + cntk;                                                                                                              \
+                        if (WRITE_VOLUME) __builtin_amdgcn_raw_buffer_store_b32(cell, rvol, pix0, 4u * (uint32_t)(j * W), 2);                                                \
+                        if (FUSED) {                                                                                                                                         \
+                            const bool better = plain_compare.value ? cell < best[j] : umul24u(cell & 0xffffffu, best[j] >> 24) < umul24u(best[j] & 0xffffffu, cell >> 24);  \
+                            best[j] = better ? cell : best[j];                                                                                                               \
+                            bi[j] = better ? d0 + k : bi[j];                                                                                                                 \
+                        }                                                                                                                                                    \
+                    }                                                                                                                                                        \
+                }                                                                                                                                                            \
+            }                                                                                                                                                                \
+        }                                                                                                                                                                    \
+    };                                                                                                                                                                       \
+    if (col_ok) {                                                                                                                                                            \
+        if (nrows == 8 && plain)                                                                                                                                             \
+            finish(std::false_type{}, std::true_type{});                                                                                                                     \
+        else if (nrows == 8)                                                                                                                                                 \
+            finish(std::false_type{}, std::false_type{});                                                                                                                    \
+        else if (plain)                                                                                                                                                      \
+            finish(std::true_type{}, std::true_type{});                                                                                                                      \
+        else                                                                                                                                                                 \
+            finish(std::true_type{}, std::false_type{});                                                                                                                     \
+    }                                                                                                                                                                        \
+    _Pragma("unroll")                                                                                                                                                        \
+    for (int k = 0; k < RX_KW; k++)                                                                                                                                          \
+    _Pragma("unroll")                                                                                                                                                        \
+        for (int j = 0; j < 8; j++) acc[j][k] = 0u;                                                                                                                          \
+    spacc = 0u;                                                                                                                                                              \
+    vleft = a.vcount;                                                                                                                                                        \
+    chunk++;
 
     for (int r = nreg; r > 0; r--) {
         // every copy and every record this wavefront asked for has landed ...
@@ -509,15 +583,20 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
         // the record of region r + 1 and the copy of region r + 1 into the other slot (nothing behind a workgroup's last region: its
         // record ends the copy where it starts): in flight during this region's sampling
         xl = load_rec(xo);
-        yl = load_rec(xo + ydelta);
+        yl = load_rec(yo);
         xo += 4u * 4u * RX_REC;
-        issue_copy(rdl(rsum, 4), rdl(rsum, 5), slot_cur ^ slot_bytes);
+        yo += 4u * 4u * RX_REC;
+        issue_copy(rdl(rsum, 4), rdl(rsum, 5), copy_flip - slot_cur);
+        // the previous turn ended a chunk: its epilogue, before this turn's sampling adds to the accumulators and to spacc
+        if (__builtin_expect(vleft == 0, 0)) {
+            RX_CHUNK_EPILOGUE
+        }
         const uint32_t we[RX_KW] = {rdl(rsum, 6), rdl(rsum, 7), rdl(rsum, 8), rdl(rsum, 9)};
         const uint32_t fld[RX_KW] = {rdl(rsum, 0), rdl(rsum, 1), rdl(rsum, 2), rdl(rsum, 3)};  // per plane: LDS byte offset, or a flag bit
 
         // ---- sample region r ----
         {
-            const uint32_t slot_byte = lds_base + slot_cur;
+            const uint32_t slot_byte = slot_cur;
             uint32_t qd[1][8];
             const uint32_t clean = rdl(rsum, 10);  // 0: CLEAN (no flag in a field, no mask byte)
             {
@@ -720,62 +799,15 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
             }
         }
 
-        // ---- chunk epilogue ----
-        if (--vleft == 0) {
-            const int d0 = chunk * RX_PC + wave * RX_KW;
-            const size_t P = (size_t)a.W * a.H;
-            const uint32_t pix0 = 4u * (uint32_t)(row0 * a.W + col);  // byte offset of this lane's first pixel inside a plane
-            const int nrows = min(8, a.H - row0);
-            // While every plane of every chunk so far was FULL for every view, every cell carries the same count and the packed cells
-            // compare like their sums: "cell < best" (best starts at 0xffffffff) instead of the cross-multiplied comparison.  The
-            // first chunk with a plane that is not FULL ends that for the rest of the workgroup (same packed cells, start value 1).
-            if (FUSED && plain && spacc != 0u) {
-                plain = false;
-#pragma unroll
-                for (int j = 0; j < 8; j++) best[j] = bi[j] < 0 ? 1u : best[j];
-            }
-            auto finish = [&](auto checked_rows, auto plain_compare) {
-#pragma unroll
-                for (int k = 0; k < RX_KW; k++) {
-                    const uint32_t cntk = ((uint32_t)a.vcount - ((spacc >> (8 * k)) & 0xffu)) << 24;  // FULL planes: every cell gets the view's count
-                    if (d0 + k < a.D) {
-                        // one resource per plane (a volume can exceed the 4 GiB a resource spans), rows by the wave-uniform offset
-                        const __amdgpu_buffer_rsrc_t rvol = make_rsrc(WRITE_VOLUME ? a.volume + (size_t)(d0 + k) * P : nullptr, 0xffffffffu);
-#pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            if (!checked_rows.value || j < nrows) {
-                                const uint32_t cell = acc[j][k] + cntk;
-                                if (WRITE_VOLUME) __builtin_amdgcn_raw_buffer_store_b32(cell, rvol, pix0, 4u * (uint32_t)(j * a.W), 2);  // nt: written once, read by a later kernel
-                                if (FUSED) {
-                                    const bool better = plain_compare.value ? cell < best[j] : umul24u(cell & 0xffffffu, best[j] >> 24) < umul24u(best[j] & 0xffffffu, cell >> 24);
-                                    best[j] = better ? cell : best[j];
-                                    bi[j] = better ? d0 + k : bi[j];
-                                }
-                            }
-                        }
-                    }
-                }
-            };
-            if (col_ok) {
-                if (nrows == 8 && plain)
-                    finish(std::false_type{}, std::true_type{});
-                else if (nrows == 8)
-                    finish(std::false_type{}, std::false_type{});
-                else if (plain)
-                    finish(std::true_type{}, std::true_type{});
-                else
-                    finish(std::true_type{}, std::false_type{});
-            }
-#pragma unroll
-            for (int k = 0; k < RX_KW; k++)
-#pragma unroll
-                for (int j = 0; j < 8; j++) acc[j][k] = 0u;
-            spacc = 0u;
-            vleft = a.vcount;
-            chunk++;
-        }
-        slot_cur ^= slot_bytes;
+        // the chunk's last view: its epilogue is left pending for the next turn (or for the lines behind the loop)
+        --vleft;
+        slot_cur = slot_flip - slot_cur;
     }
+
+    if (nreg > 0) {  // the workgroup's last chunk: the last turn ended it
+        RX_CHUNK_EPILOGUE
+    }
+#undef RX_CHUNK_EPILOGUE
 
     // ---- depth selection across the four wavefronts (each holds the best of its own planes): lowest cost, ties -> lowest plane ----
     if (FUSED) {
