@@ -214,7 +214,12 @@ int mvs_sweep_argmin(mvs_ctx *ctx);
  * with a neighbour that no view sees, keep their depth).  Needs the packed volume and a depth selection of the same run
  * (MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN, or MVS_SWEEP_VOLUME + mvs_sweep_argmin); best cost and index are unchanged.
  * The plane step is what makes two samplers that pick neighbouring planes of equal cost differ by 1/D in depth; refined depths of the
- * two samplers agree to a small fraction of it. */
+ * two samplers agree to a small fraction of it.
+ * Errors: MVS_ESTATE without planes, a packed volume or a depth selection; MVS_ESTATE when the depth selection was made over another
+ * plane count than the current one (mvs_sweep_set_planes with a new nplanes since: select again; the same nplanes changes nothing;
+ * fused row-band runs over new planes count as a selection once their bands, each touching the last, cover every row);
+ * MVS_EINVAL when the caller's volume (mvs_sweep_use_volume) is smaller than nplanes * H * W cells, MVS_ESTATE when the context's own is
+ * (allocated for fewer planes).  A refused call launches nothing: the maps are untouched. */
 int mvs_sweep_refine_depth(mvs_ctx *ctx);
 /* Semi-global aggregation of the packed volume before depth selection (DESIGN.md section 13 is the arithmetic contract; exact integer
  * arithmetic, bit-identical to tests/sgm_mirror.py).  Every cell's matching cost C = min(floor(16 mean cost), cost_cap) in 1/16 grey levels
@@ -252,9 +257,10 @@ int mvs_sweep_aggregate_fetch(mvs_ctx *ctx, uint16_t *s_dhw);
  * the same parameters rejects nothing the second time.  mvs_sweep_clean_report synchronises: pixels with an index before the call, and
  * pixels rejected by rule 1, 2, 3.
  * Errors: MVS_EINVAL for a NULL ctx or array, a parameter outside its range, unknown flag bits; MVS_ESTATE without a depth selection,
- * for min_views >= 2 or uniqueness_percent > 0 without a packed volume of nplanes * H * W cells (min_views 1 is tested where the context has
- * one), for MVS_CLEAN_SCORES_AGGREGATED without an S of the current plane count, for mvs_sweep_clean_report before the first clean and
- * for mvs_sweep_clean_sizes_fetch unless the last clean ran rule 3 (mvs_sweep_clean_sizes_device: NULL then); MVS_ENOMEM.  After an error
+ * for a depth selection made over another plane count than the current one (mvs_sweep_set_planes with a new nplanes since), for
+ * min_views >= 2 or uniqueness_percent > 0 without a packed volume of nplanes * H * W cells (min_views 1 is tested where the context
+ * has one), for MVS_CLEAN_SCORES_AGGREGATED without an S of the current plane count, for mvs_sweep_clean_report before the first clean
+ * and for mvs_sweep_clean_sizes_fetch unless the last clean ran rule 3 (mvs_sweep_clean_sizes_device: NULL then); MVS_ENOMEM.  After an error
  * the maps are untouched.  Speckle-only cleaning needs no volume (it works after an MVS_SWEEP_FUSED_ARGMIN run). */
 #define MVS_CLEAN_SCORES_AGGREGATED 1u
 int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int speckle_min_size, int speckle_max_diff, unsigned flags);

@@ -388,6 +388,7 @@ int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, u
                                                                       (float *)ctx->cost.ptr, (int *)ctx->index.ptr);
     MVS_HIP(ctx, hipGetLastError());
     ctx->agg_planes = D;
+    note_full_selection(ctx);
     return MVS_OK;
 }
 

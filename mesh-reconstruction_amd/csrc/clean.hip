@@ -275,9 +275,11 @@ int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int spe
     if (speckle_min_size < 0) return fail(ctx, MVS_EINVAL, "mvs_sweep_clean: speckle_min_size %d is negative", speckle_min_size);
     if (speckle_max_diff < 0 || speckle_max_diff > 255) return fail(ctx, MVS_EINVAL, "mvs_sweep_clean: speckle_max_diff %d outside 0..255", speckle_max_diff);
     if (flags & ~MVS_CLEAN_SCORES_AGGREGATED) return fail(ctx, MVS_EINVAL, "mvs_sweep_clean: unknown flag bits 0x%x", flags & ~MVS_CLEAN_SCORES_AGGREGATED);
-    if (!ctx->index.ptr || !ctx->depth.ptr || !ctx->cost.ptr)
+    if (!ctx->index.ptr || !ctx->depth.ptr || !ctx->cost.ptr || !ctx->sel_planes)
         return fail(ctx, MVS_ESTATE, "mvs_sweep_clean: no depth selection yet (mvs_sweep_run with MVS_SWEEP_FUSED_ARGMIN, mvs_sweep_argmin or mvs_sweep_aggregate)");
     const int W = ctx->W, H = ctx->H, D = ctx->D;
+    if (ctx->sel_planes != D)   // rules 1 and 2 read the volume (and S) at the selected plane
+        return fail(ctx, MVS_ESTATE, "mvs_sweep_clean: the depth selection was made over %d planes, the context now has %d (select again)", ctx->sel_planes, D);
     const size_t P = (size_t)W * H;
     if (P > (size_t)INT_MAX) return fail(ctx, MVS_EINVAL, "mvs_sweep_clean: %zu pixels do not fit the 32-bit labels", P);
     const bool agg = (flags & MVS_CLEAN_SCORES_AGGREGATED) != 0;

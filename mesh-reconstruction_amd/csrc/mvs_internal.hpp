@@ -49,6 +49,10 @@ struct mvs_ctx {
     size_t volume_bytes = 0;
     bool volume_external = false;
     mvs::DevBuf depth, cost, index;  // H*W each
+    int sel_planes = 0;              // plane count EVERY row of the index map was last selected over (0: no depth selection yet); set by the host
+                                     // entries that launch a writer of `index`, compared with D by mvs_sweep_refine_depth and mvs_sweep_clean
+    int sel_band_planes = 0;         // fused row-band runs over a plane count other than sel_planes: that count and the rows [lo, hi) the
+    int sel_band_lo = 0, sel_band_hi = 0;  // bands cover so far; sel_planes follows when they cover all rows (sweep.hip: note_selection)
     int pad_pitch = 0;
     size_t pad_slab = 0;             // bytes per padded side image
     int V = 0, D = 0;
@@ -231,6 +235,13 @@ int tsdf_ensure_field(mvs_ctx *ctx, int min_obs);
 int tsdf_ensure_appearance(mvs_ctx *ctx);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
+
+// a writer of every row of ctx->index has been launched over the current planes (mvs_ctx::sel_planes)
+inline void note_full_selection(mvs_ctx *ctx)
+{
+    ctx->sel_planes = ctx->D;
+    ctx->sel_band_planes = 0;
+}
 
 // the sweep's input setters with the final synchronisation optional (context.hip; mvs_sweep queues all of them and waits once)
 int sweep_set_main_impl(mvs_ctx *ctx, const float main_cam[16], const uint8_t *main_hw, bool sync, bool device = false);

@@ -777,6 +777,26 @@ struct SweepRange {
 
 static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags);
 
+// a fused run has rewritten rows [r0, r1) of the index map over the current planes.  The whole image, or bands over the plane count the
+// map already has, leave a selection over D planes; bands over another count leave one only once they -- each overlapping or touching
+// what the earlier ones covered -- reach every row: until then the other rows hold planes of the old count and there is no selection
+static void note_selection(mvs_ctx *ctx, int r0, int r1)
+{
+    const int D = ctx->D;
+    if (r0 <= 0 && r1 >= ctx->H) return note_full_selection(ctx);
+    if (ctx->sel_planes == D) return;
+    ctx->sel_planes = 0;  // rows of two plane counts: no selection until the bands are through
+    if (ctx->sel_band_planes != D || r0 > ctx->sel_band_hi || r1 < ctx->sel_band_lo) {
+        ctx->sel_band_planes = D;
+        ctx->sel_band_lo = r0;
+        ctx->sel_band_hi = r1;
+    } else {
+        ctx->sel_band_lo = r0 < ctx->sel_band_lo ? r0 : ctx->sel_band_lo;
+        ctx->sel_band_hi = r1 > ctx->sel_band_hi ? r1 : ctx->sel_band_hi;
+    }
+    if (ctx->sel_band_lo <= 0 && ctx->sel_band_hi >= ctx->H) note_full_selection(ctx);
+}
+
 int mvs_sweep_run(mvs_ctx *ctx, int view_first, int view_count, unsigned flags)
 {
     if (!ctx) return MVS_EINVAL;
@@ -996,7 +1016,9 @@ static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags)
     int rc = ensure_outputs(ctx, f.vol);
     if (rc) return rc;
     if (r.row_count <= 0 || r.plane_count <= 0) return MVS_OK;  // empty band or empty plane group: nothing to compute
-    return ctx->sampler == MVS_SAMPLER_FIXED ? sweep_run_fixed(ctx, r, f) : sweep_run_exact(ctx, r, f);
+    rc = ctx->sampler == MVS_SAMPLER_FIXED ? sweep_run_fixed(ctx, r, f) : sweep_run_exact(ctx, r, f);
+    if (rc == MVS_OK && f.fused) note_selection(ctx, r.row_first, r.row_first + r.row_count);
+    return rc;
 }
 
 // depth selection over `vol` with the cell layout of the context's sampler; 16-byte loads when the pixel count and the pointer allow
@@ -1029,16 +1051,25 @@ int mvs_sweep_argmin(mvs_ctx *ctx)
     launch_argmin(ctx, ctx->volume, P, ctx->D, (const float *)ctx->ztab.ptr, (float *)ctx->depth.ptr, (float *)ctx->cost.ptr, (int *)ctx->index.ptr,
                   nullptr, 0);
     MVS_HIP(ctx, hipGetLastError());
+    note_full_selection(ctx);
     return MVS_OK;
 }
 
 int mvs_sweep_refine_depth(mvs_ctx *ctx)
 {
     if (!ctx) return MVS_EINVAL;
-    if (!ctx->have_planes || !ctx->volume || !ctx->index.ptr)
+    if (!ctx->have_planes || !ctx->volume || !ctx->index.ptr || !ctx->sel_planes)
         return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: needs the packed volume and a depth selection (MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN, or mvs_sweep_argmin)");
+    // the kernel reads z[index] and the cells of planes index - 1 .. index + 1: the index map must be one over the current planes ...
+    if (ctx->sel_planes != ctx->D)
+        return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: the depth selection was made over %d planes, the context now has %d (select again)", ctx->sel_planes, ctx->D);
+    // ... and the volume must hold them (ensure_outputs and mvs_sweep_aggregate refuse the same)
+    const size_t P = (size_t)ctx->W * ctx->H, need = P * (size_t)ctx->D * sizeof(uint32_t);
+    if (ctx->volume_bytes < need) {
+        if (ctx->volume_external) return fail(ctx, MVS_EINVAL, "mvs_sweep_refine_depth: caller volume is %zu bytes, %d planes need %zu", ctx->volume_bytes, ctx->D, need);
+        return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: the context's volume is %zu bytes, %d planes need %zu (mvs_sweep_run with MVS_SWEEP_VOLUME)", ctx->volume_bytes, ctx->D, need);
+    }
     MVS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t P = (size_t)ctx->W * ctx->H;
     if (ctx->sampler == MVS_SAMPLER_FIXED)
         refine_depth<CS_FIXED><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(ctx->volume, P, ctx->D, (const float *)ctx->ztab.ptr, (const int *)ctx->index.ptr, (float *)ctx->depth.ptr);
     else
@@ -1078,6 +1109,7 @@ int mvs_sweep_combine_partials(mvs_ctx *ctx, const void *partials_dev, int npart
     else
         combine_best<CS_EXACT><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(p, nparts, 0, P);
     MVS_HIP(ctx, hipGetLastError());
+    note_full_selection(ctx);
     return MVS_OK;
 }
 

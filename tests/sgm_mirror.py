@@ -129,21 +129,15 @@ def _fma32(a, b, c):
     return r.astype(np.float32)
 
 
-def refine(S, seen, z, index):
-    """rule 5: depth map with the parabola of mvs_sweep_refine_depth on (float)S, f32 with one rounding per operation"""
-    S = np.asarray(S)
-    D, H, W = S.shape
+def parabola(ca, cb, cc, ok, z, index):
+    """the parabola of mvs_sweep_refine_depth through the f32 costs ca, cb, cc of the planes index - 1, index, index + 1 ([H, W] each; `ok`:
+    the pixel has all three), f32 with one rounding per operation and the final fused multiply-add; a pixel that is not `ok`, or whose
+    den is not positive, keeps z[index] (the background depth without an index).  Needs at least three planes."""
     z = np.asarray(z, np.float32)
-    i = np.clip(index, 1, D - 2).astype(np.int64)[None]
-    ca = np.take_along_axis(S, i - 1, axis=0)[0].astype(np.float32)
-    cb = np.take_along_axis(S, i, axis=0)[0].astype(np.float32)
-    cc = np.take_along_axis(S, i + 1, axis=0)[0].astype(np.float32)
-    ok = (index > 0) & (index < D - 1)
-    for k in (-1, 0, 1):
-        ok &= np.take_along_axis(seen, i + k, axis=0)[0]
-    i = i[0]
+    D = len(z)
+    i = np.clip(index, 1, D - 2).astype(np.int64)
     den = (ca - np.float32(2.0) * cb) + cc
-    ok &= den > 0
+    ok = ok & (den > 0)
     with np.errstate(divide="ignore", invalid="ignore"):
         t = (np.float32(0.5) * (ca - cc)) / den
     t = np.where(ok, t, np.float32(0)).astype(np.float32)
@@ -154,3 +148,17 @@ def refine(S, seen, z, index):
     zr = np.where(t >= 0, fwd, bwd)
     plain = np.where(index >= 0, z[np.clip(index, 0, D - 1)], BACKGROUND_DEPTH)
     return np.where(ok, zr, plain).astype(np.float32)
+
+
+def refine(S, seen, z, index):
+    """rule 5: depth map with the parabola of mvs_sweep_refine_depth on (float)S, f32 with one rounding per operation"""
+    S = np.asarray(S)
+    D, H, W = S.shape
+    i = np.clip(index, 1, D - 2).astype(np.int64)[None]
+    ca = np.take_along_axis(S, i - 1, axis=0)[0].astype(np.float32)
+    cb = np.take_along_axis(S, i, axis=0)[0].astype(np.float32)
+    cc = np.take_along_axis(S, i + 1, axis=0)[0].astype(np.float32)
+    ok = (index > 0) & (index < D - 1)
+    for k in (-1, 0, 1):
+        ok &= np.take_along_axis(seen, i + k, axis=0)[0]
+    return parabola(ca, cb, cc, ok, z, index)
