@@ -323,6 +323,45 @@ int mvs_sweep_batch_async(mvs_ctx *ctx, int nmain, const int *main_slots, const 
                           const float *side_cams, int nplanes, float z_lo, float z_hi, float *depth_out, float *cost_out);
 int mvs_sweep_batch_wait(mvs_ctx *ctx);
 
+/* ---- lens: distorted frames -> the pinhole frames the cameras describe (csrc/lens.hip) ------------------------
+ * The cameras of a tracks file are a tracker's solution for UNDISTORTED image coordinates; the frames that go with them are as the lens
+ * saw them.  A context can carry the clip's radial lens model -- the reference's cameraToScreen (configuration.cpp:248-259) with the
+ * pixel mapping of configuration.cpp:292-293 -- and resample frames through it on the device: for every pixel centre of the output
+ * (pinhole) frame the model gives the position in the distorted frame, which is sampled with mvs_flow_remap's fixed-point bicubic rule
+ * (1/32-pixel positions, Q15 weights) and a REPLICATED border (a tap outside the frame takes the nearest frame pixel; every output
+ * pixel is written).  The arithmetic is f32 with one rounding per operation, stated in DESIGN.md section 17 and restated by
+ * tests/lens_mirror.py; the device is bit-identical to it.  With zero coefficients and the centre at (W/2, H/2) the output is the input.
+ * Opt-in: a context without a lens behaves exactly as before, and nothing is allocated for one.
+ *   mvs_set_lens(ctx, k, cx, cy)     k = the three radial coefficients (distortion: [k1, k2, k3] of the tracks file; the reference uses
+ *                                    two), (cx, cy) = the clip's center-x / center-y in pixels of the context's frame, cy measured from
+ *                                    the BOTTOM as the tracks files do.  k == NULL clears the lens.  Touches nothing already uploaded.
+ *                                    MVS_EINVAL for a non-finite coefficient or centre, |k_i| > MVS_LENS_MAX_COEFFICIENT, or a lens whose
+ *                                    radial map rho -> rho k(rho^2) folds over inside the frame: d/d rho = 1 + 3 k1 rho^2 + 5 k2 rho^4 +
+ *                                    7 k3 rho^6 <= 0, in double, at one of the 1024 radii rho_max i / 1024, i = 1..1024, rho_max^2 =
+ *                                    (1 + (H/W)^2) / 4 (the farthest corner in the model's units).
+ *   mvs_lens(ctx, k, &cx, &cy)       1 and the lens (each pointer nullable) when one is set, 0 when none
+ *   mvs_undistort(ctx, src, dst)     one frame, host buffers (H*W u8 each); synchronises
+ *   mvs_undistort_device(ctx, src, dst, n)   n (1..65535) tightly packed H*W frames on the context's GPU in one launch; asynchronous and
+ *                                    stream-ordered like mvs_frame_upload_device; MVS_EINVAL when the two ranges overlap (src == dst too)
+ *   mvs_undistort_map(ctx, map)      diagnostic: the source position (x, y), in pixel indices of the distorted frame, of every output
+ *                                    pixel (H*W*2 f32), computed by the device; synchronises
+ *   mvs_frame_upload_lens(ctx, slot, f) / mvs_frame_upload_lens_device: mvs_frame_upload / _device with the frame taken through the lens
+ *                                    on its way into the store: the slot's bytes (raw frame and quad image) are those of mvs_undistort
+ *                                    followed by mvs_frame_upload, so everything that reads slots (mvs_sweep_handles, mvs_sweep_batch*,
+ *                                    mvs_process_frame_slots, mvs_tsdf_integrate_frames) sees pinhole frames.  A host frame is staged in
+ *                                    a W*H device buffer allocated by the first such call.
+ * Errors: MVS_EINVAL for a NULL ctx or pointer and for a slot outside the store (an unsized store has no slots); MVS_ESTATE from all but
+ * mvs_set_lens and mvs_lens when no lens is set; MVS_ENOMEM.  After an error nothing is written.  The launches are timed under
+ * MVS_K_PROJECT. */
+#define MVS_LENS_MAX_COEFFICIENT 16
+int mvs_set_lens(mvs_ctx *ctx, const float k[3], float center_x, float center_y);
+int mvs_lens(mvs_ctx *ctx, float k_out[3], float *center_x, float *center_y);
+int mvs_undistort(mvs_ctx *ctx, const uint8_t *src_hw, uint8_t *dst_hw);
+int mvs_undistort_device(mvs_ctx *ctx, const void *src_dev, void *dst_dev, int nframes);
+int mvs_undistort_map(mvs_ctx *ctx, float *map_hw2);
+int mvs_frame_upload_lens(mvs_ctx *ctx, int slot, const uint8_t *frame_hw);
+int mvs_frame_upload_lens_device(mvs_ctx *ctx, int slot, const void *frame_dev);
+
 /* ---- depth store + fusion: depth maps of a sequence -> one multi-view-consistent oriented point cloud (csrc/fuse.hip) ----
  * The store keeps depth maps in the library's convention (main-camera NDC z, 1.0 = empty: a sweep's result, or mvs_depth of a mesh) with
  * their best costs and cameras in HBM.  Life cycle as the frame store's: mvs_depth_store sizes it (1..8191 slots, re-sizing empties it);
@@ -534,7 +573,7 @@ int mvs_comm_device(const mvs_comm *comm, int rank);
 #define MVS_K_ARGMIN 1
 #define MVS_K_PLAN 2
 #define MVS_K_RASTER 3
-#define MVS_K_PROJECT 4
+#define MVS_K_PROJECT 4 /* Render::projected; the lens launches (mvs_undistort, _device, _map, mvs_frame_upload_lens*) */
 #define MVS_K_FLOW 5
 #define MVS_K_FUSE 6 /* mvs_fuse_depth: count pass, scan, row pass */
 #define MVS_K_TSDF 7 /* mvs_tsdf_integrate: w-map passes and integration launches; mvs_tsdf_raycast: field, brick mask, ray kernel; mvs_tsdf_integrate_frames, _shade, _sample_appearance */

@@ -276,7 +276,7 @@ void mvs_destroy(mvs_ctx *ctx)
                       &ctx->dstore_depth, &ctx->dstore_cost, &ctx->fuse_rows, &ctx->fuse_counts, &ctx->fuse_scan,
                       &ctx->tsdf_vol, &ctx->tsdf_wmaps, &ctx->tsdf_work, &ctx->tsdf_bricks, &ctx->ray_depth, &ctx->ray_normals, &ctx->agg_cost, &ctx->agg_sum,
                       &ctx->clean_labels, &ctx->clean_sizes, &ctx->clean_counters,
-                      &ctx->tsdf_app, &ctx->shade_map, &ctx->app_points};
+                      &ctx->tsdf_app, &ctx->shade_map, &ctx->app_points, &ctx->lens_stage};
     for (DevBuf *b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto &lane : ctx->lanes)
@@ -476,17 +476,34 @@ int frame_store_impl(mvs_ctx *ctx, int capacity)
     return MVS_OK;
 }
 
-int frame_upload_impl(mvs_ctx *ctx, int slot, const uint8_t *frame_hw, bool device)
+// lens: the frame goes through the context's lens (lens.hip) into the raw slot instead of being copied there; everything after that is the same
+int frame_upload_impl(mvs_ctx *ctx, int slot, const uint8_t *frame_hw, bool device, bool lens = false)
 {
-    if (!ctx || !frame_hw) return fail(ctx, MVS_EINVAL, "mvs_frame_upload: null argument");
-    if (slot < 0 || slot >= ctx->store_cap) return fail(ctx, MVS_EINVAL, "mvs_frame_upload: slot %d outside the store (capacity %d: mvs_frame_store first)", slot, ctx->store_cap);
+    const char *who = lens ? "mvs_frame_upload_lens" : "mvs_frame_upload";
+    if (!ctx || !frame_hw) return fail(ctx, MVS_EINVAL, "%s: null argument", who);
+    if (lens && !ctx->lens_set) return fail(ctx, MVS_ESTATE, "%s: no lens is set (mvs_set_lens)", who);
+    if (slot < 0 || slot >= ctx->store_cap) return fail(ctx, MVS_EINVAL, "%s: slot %d outside the store (capacity %d: mvs_frame_store first)", who, slot, ctx->store_cap);
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const int W = ctx->W, H = ctx->H;
     const size_t P = (size_t)W * H;
     const int pitch = ((W + 2 + 63) / 64) * 64;
     const size_t slab = (size_t)pitch * (H + 2);
     uint8_t *raw = (uint8_t *)ctx->store_raw.ptr + P * slot;
-    MVS_HIP(ctx, hipMemcpyAsync(raw, frame_hw, P, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    if (!lens) {
+        MVS_HIP(ctx, hipMemcpyAsync(raw, frame_hw, P, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        // the resampling needs source != destination: a host frame, or a device frame that overlaps the slot itself, is staged
+        const uint8_t *src = frame_hw;
+        const uintptr_t s = (uintptr_t)frame_hw, d = (uintptr_t)raw;
+        if (!device || (s < d + P && d < s + P)) {
+            int rc = ensure(ctx, ctx->lens_stage, P);
+            if (rc) return rc;
+            MVS_HIP(ctx, hipMemcpyAsync(ctx->lens_stage.ptr, frame_hw, P, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+            src = (const uint8_t *)ctx->lens_stage.ptr;
+        }
+        int rc = undistort_launch(ctx, src, raw, 1);
+        if (rc) return rc;
+    }
     const dim3 grid(div_up(pitch / 4, 256), H + 2, 1);
     quad_image_from_raw_kernel<<<grid, 256, 0, ctx->stream>>>(raw, P, nullptr, (uint32_t *)ctx->store_quads.ptr + slab * slot, W, H, pitch, slab, 0);
     MVS_HIP(ctx, hipGetLastError());
@@ -603,6 +620,8 @@ int mvs_texture_filter(const mvs_ctx *ctx) { return ctx ? ctx->texture_filter : 
 int mvs_frame_store(mvs_ctx *ctx, int capacity) { return frame_store_impl(ctx, capacity); }
 int mvs_frame_upload(mvs_ctx *ctx, int slot, const uint8_t *frame_hw) { return frame_upload_impl(ctx, slot, frame_hw, false); }
 int mvs_frame_upload_device(mvs_ctx *ctx, int slot, const void *frame_dev) { return frame_upload_impl(ctx, slot, (const uint8_t *)frame_dev, true); }
+int mvs_frame_upload_lens(mvs_ctx *ctx, int slot, const uint8_t *frame_hw) { return frame_upload_impl(ctx, slot, frame_hw, false, true); }
+int mvs_frame_upload_lens_device(mvs_ctx *ctx, int slot, const void *frame_dev) { return frame_upload_impl(ctx, slot, (const uint8_t *)frame_dev, true, true); }
 
 int mvs_sweep_view_matrices(mvs_ctx *ctx, float *q_out)
 {

@@ -140,6 +140,12 @@ struct mvs_ctx {
     std::vector<hipEvent_t> band_events;  // mvs_sweep's band pipeline: rows uploaded / band swept, per band
     int store_cap = 0;
     std::vector<unsigned char> store_have;
+    // lens (lens.hip: mvs_set_lens / mvs_undistort* / mvs_frame_upload_lens): the radial coefficients and the centre in pixels (y from the
+    // bottom) while lens_set; lens_stage is the W*H staging frame of mvs_frame_upload_lens, allocated by its first use
+    bool lens_set = false;
+    float lens_k[3] = {0.f, 0.f, 0.f};
+    float lens_cx = 0.f, lens_cy = 0.f;
+    mvs::DevBuf lens_stage;
     // mvs_process_frame runs the flows of one main frame's side views concurrently, one lane each:
     // A lane: the stream one side view's flow runs on, a SHADOW context that stands for this context on that stream (device, size, hooks; its own flow
     // arena; nothing else is used through it) and a host thread that queues the flow's launches while the calling thread goes on with the next side
@@ -267,6 +273,8 @@ int remap_device(mvs_ctx *ctx, const float *flow, int stride, const uint8_t *img
 int compare_batch_device(mvs_ctx *ctx, const uint8_t *prev8, const uint8_t *next8, int B, float *out);
 int remap_batch_device(mvs_ctx *ctx, const float *flow, int stride, ptrdiff_t flow_z, const uint8_t *img, int B, uint8_t *out);
 int ensure_cubic_table(mvs_ctx *ctx);
+// lens.hip: nframes tightly packed W*H frames through the context's lens in one launch on ctx->stream (lens set, ranges disjoint: the caller checks)
+int undistort_launch(mvs_ctx *ctx, const uint8_t *src_dev, uint8_t *dst_dev, int nframes);
 // raster.hip / flow.hip / triangulate.hip on device buffers (pipeline.hip strings them together)
 int depth_device(mvs_ctx *ctx, const float cam[16], float *out_dev);
 int projected_device(mvs_ctx *ctx, const float cam[16], const uint8_t *frame_dev, const float projector[16], uint8_t *out3_dev);

@@ -369,6 +369,9 @@ void pinvSolve(const float *A, int n, int m, const float *b, float *x)
     for (int a = 0; a < m; a++) x[a] = (float)sol[a];
 }
 
+// what estimateExposure and --undistort say about a tracks file without (two) distortion coefficients
+const char *const kNoLensDistortion = "the tracks file gives no lens distortion";
+
 }  // namespace
 
 // util.cpp:408-433: mean of the unclipped values (0 < v < 255) of one channel inside a disc; -1 when there is none
@@ -415,6 +418,7 @@ void Configuration::parseYaml(const std::string &path)
         centerY /= scalingFactor;
     }
     for (const std::string &s : clip.at("distortion").flow) lensDistortion.push_back((float)atof(s.c_str()));
+    if (undistort && lensDistortion.size() < 2) throw std::runtime_error(std::string("undistort: ") + kNoLensDistortion);
 
     bundles = Mat(0, 4, mvs::F32C1);  // configuration.cpp:176-197
     const Node *tracks = root.get("tracks");
@@ -496,7 +500,7 @@ void Configuration::colorFramesReady()
     }
     for (size_t i = 0; i < colorFrames.size(); i++)
         if (!colorFrames[i].empty()) {
-            frames[i] = bgrToGray(colorFrames[i]);
+            frames[i] = throughLens(bgrToGray(colorFrames[i]));
             colorFrames[i] = Mat();
         }
 }
@@ -523,7 +527,7 @@ void Configuration::estimateExposure()
     const int frameCount = (int)cameras.size(), pointCount = bundles.rows;
     if (frameCount == 0 || (int)colorFrames.size() != frameCount) throw std::runtime_error("estimateExposure: colour frames missing");
     const int ch = colorFrames[0].channels();
-    if (lensDistortion.size() < 2) throw std::runtime_error("estimateExposure: the tracks file gives no lens distortion");
+    if (lensDistortion.size() < 2) throw std::runtime_error(std::string("estimateExposure: ") + kNoLensDistortion);
     std::vector<float> sampledColor;                     // rows of `ch` brightness values, one per valid (frame, point) sample
     std::vector<int> sampleIds((size_t)frameCount * pointCount, -1);
     std::vector<int> rowBegin(frameCount + 1, 0);
@@ -630,13 +634,14 @@ void Configuration::estimateExposure()
             }
             d[p] = (uint8_t)acc;
         }
-        frames[i] = g;
+        frames[i] = throughLens(g);
         colorFrames[i] = Mat();
     }
 }
 
-Configuration::Configuration(const std::string &yamlPath, int skip)
+Configuration::Configuration(const std::string &yamlPath, int skip, bool undistortFrames)
 {
+    undistort = undistortFrames;
     skipFrames = skip > 0 ? skip : 1;
     parseYaml(yamlPath);
 }
@@ -653,6 +658,7 @@ Configuration::Configuration(int argc, char **argv)
                                            {"hyper-verbose", no_argument, 0, 'V'},      {"help", no_argument, 0, 'h'},
                                            {"sweep-planes", required_argument, 0, 1000},  // (not in the reference: recon.hpp's sweepPlanes)
                                            {"threads", required_argument, 0, 1001},       // (not in the reference: recon.hpp's threads)
+                                           {"undistort", no_argument, 0, 1002},           // (not in the reference: recon.hpp's undistort)
                                            {0, 0, 0, 0}};
     for (;;) {
         int option_index = 0;
@@ -677,6 +683,7 @@ Configuration::Configuration(int argc, char **argv)
         case 'V': verbosity = 99; break;
         case 1000: sweepPlanes = std::max(0, atoi(optarg)); break;
         case 1001: threads = std::min(64, std::max(1, atoi(optarg))); break;
+        case 1002: undistort = true; break;
         default:
             throw std::runtime_error("Usage: recon [OPTIONS] [INPUT_FILE]  (options: -c f, -e, -f, -h, -i s, -k i, -m s, -n i, -o s, -s f, -v, -V)");
         }
@@ -719,6 +726,24 @@ static Mat resizedToClip(const Mat &frame, int width, int height)
     return out;
 }
 
+// --undistort: the grey frame as the lens saw it -> the pinhole frame the cameras describe (mvs_set_lens + mvs_undistort with the clip's
+// distortion coefficients and its centre, which parseYaml has scaled with the clip), on a context of its own per call like resizedToClip
+Mat Configuration::throughLens(const Mat &gray) const
+{
+    if (!undistort) return gray;
+    if (lensDistortion.size() < 2) throw std::runtime_error(std::string("undistort: ") + kNoLensDistortion);
+    mvs_ctx *ctx = mvs_create(0, width, height);
+    if (!ctx) throw std::runtime_error(std::string("undistort: ") + mvs_last_error(nullptr));
+    const float k[3] = {lensDistortion[0], lensDistortion[1], lensDistortion.size() > 2 ? lensDistortion[2] : 0.f};
+    Mat out(height, width, mvs::U8C1);
+    int rc = mvs_set_lens(ctx, k, centerX, centerY);
+    if (!rc) rc = mvs_undistort(ctx, gray.ptr<uchar>(0), out.ptr<uchar>(0));
+    const std::string msg = rc ? mvs_last_error(ctx) : "";
+    mvs_destroy(ctx);
+    if (rc) throw std::runtime_error("undistort: " + msg);
+    return out;
+}
+
 void Configuration::setFrameColor(int frameNo, const Mat bgr_in)
 {
     if (bgr_in.type() != mvs::U8C3) throw std::runtime_error("setFrameColor: frame must be H x W x 3 u8");
@@ -732,5 +757,5 @@ void Configuration::setFrame(int frameNo, const Mat gray_in)
     if (gray_in.type() != mvs::U8C1) throw std::runtime_error("setFrame: frame must be H x W u8");
     // (the reference resizes the decoded BGR frame and converts to grey afterwards; a grey frame of another size is resized as is)
     const Mat gray = (gray_in.cols != width || gray_in.rows != height) ? resizedToClip(gray_in, width, height) : gray_in;
-    frames.at(frameNo) = gray;
+    frames.at(frameNo) = throughLens(gray);
 }

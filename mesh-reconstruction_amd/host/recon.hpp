@@ -73,7 +73,7 @@ void setPoissonSimplify(bool on);
 class Configuration {
 public:
     Configuration(int argc, char **argv);      // same 12 getopt options as configuration.cpp:37-53
-    explicit Configuration(const std::string &yamlPath, int skipFrames = 1);
+    explicit Configuration(const std::string &yamlPath, int skipFrames = 1, bool undistort = false);
     Mat reconstructedPoints();                 // bundles, N x 4            configuration.cpp:432-435
     const Mat frame(int frameNo) const;        // H x W u8                  configuration.cpp:437-440
     const Mat camera(int frameNo) const;       // 4 x 4 f32                 configuration.cpp:442-445
@@ -102,6 +102,9 @@ public:
     float centerX = 0, centerY = 0;
     bool doEstimateExposure = false;
     int sweepPlanes = 0;           // --sweep-planes N (long option only; not in the reference): 0 = the reference's path, N > 0 = trackMainFrame's swept depth
+    bool undistort = false;        // --undistort (long option only; not in the reference, whose configuration.cpp:231 says "todo: undistort!"): every grey frame
+                                   // goes through the clip's lens model (distortion, centre) into the pinhole frame the cameras describe, on the device
+                                   // (mvs_set_lens + mvs_undistort), as the last step after resize and BGR2GRAY / the exposure mix
     int threads = 1;               // --threads N (long option only; not in the reference): reconstructPoints runs the main frames of one outer iteration on N host
                                    // threads, each with a renderer and contexts of its own on the one GPU (the `fa` loop's iterations are independent)
 
@@ -110,6 +113,7 @@ protected:
     std::vector<Mat> frames;
     std::vector<Mat> colorFrames;  // kept until the exposure estimate has turned them into `frames`
     void colorFramesReady();
+    Mat throughLens(const Mat &gray) const;         // `gray` itself unless `undistort`
     Mat resizedToClipSize(const Mat &frame) const;  // configuration.cpp:232-233 (cv::resize, bilinear) through mvs_resize_u8
     std::vector<Mat> cameras;
     std::vector<float> nearVals, farVals;

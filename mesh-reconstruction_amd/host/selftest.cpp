@@ -396,10 +396,11 @@ static int run_exposure(const std::string &yaml, const std::string &out)
     return 0;
 }
 
-// host_selftest frames <tracks yaml> <out dir> [skip]: the grey frames Configuration ends up with (clip decoding -> resize -> BGR2GRAY)
-static int run_frames(const std::string &yaml, const std::string &out, int skip)
+// host_selftest frames <tracks yaml> <out dir> [skip] [undistort]: the grey frames Configuration ends up with (clip decoding -> resize ->
+// BGR2GRAY, and with the word `undistort` the --undistort option's pass through the clip's lens)
+static int run_frames(const std::string &yaml, const std::string &out, int skip, bool undistort)
 {
-    Configuration config(yaml, skip);
+    Configuration config(yaml, skip, undistort);
     int have = 0;
     for (int i = 0; i < config.frameCount(); i++) {
         Mat g;
@@ -597,7 +598,7 @@ int main(int argc, char **argv)
         if (argc >= 8 && !strcmp(argv[1], "sequence")) return run_sequence(argc, argv);
         if (argc >= 10 && !strcmp(argv[1], "sweep")) return run_sweep(argc, argv);
         if (argc >= 4 && !strcmp(argv[1], "exposure")) return run_exposure(argv[2], argv[3]);
-        if (argc >= 4 && !strcmp(argv[1], "frames")) return run_frames(argv[2], argv[3], argc > 4 ? atoi(argv[4]) : 1);
+        if (argc >= 4 && !strcmp(argv[1], "frames")) return run_frames(argv[2], argv[3], argc > 4 ? atoi(argv[4]) : 1, argc > 5 && !strcmp(argv[5], "undistort"));
         if (argc >= 7 && !strcmp(argv[1], "choose")) return run_choose(argc, argv);
         if (argc >= 3 && !strcmp(argv[1], "cpu")) return run_cpu(argv[2]);
         if (argc >= 4 && !strcmp(argv[1], "gpu")) return run_gpu(argv[2], argv[3]);

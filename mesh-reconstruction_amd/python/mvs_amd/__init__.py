@@ -78,6 +78,13 @@ ABI = [
     ("mvs_frame_store", _i, [_vp, _i]),
     ("mvs_frame_upload", _i, [_vp, _i, _vp]),
     ("mvs_frame_upload_device", _i, [_vp, _i, _vp]),
+    ("mvs_set_lens", _i, [_vp, _fp, _f, _f]),
+    ("mvs_lens", _i, [_vp, _fp, _fp, _fp]),
+    ("mvs_undistort", _i, [_vp, _u8p, _u8p]),
+    ("mvs_undistort_device", _i, [_vp, _vp, _vp, _i]),
+    ("mvs_undistort_map", _i, [_vp, _fp]),
+    ("mvs_frame_upload_lens", _i, [_vp, _i, _vp]),
+    ("mvs_frame_upload_lens_device", _i, [_vp, _i, _vp]),
     ("mvs_sweep_handles", _i, [_vp, _i, _fp, _i, _vp, _vp, _i, _f, _f, _vp, _vp]),
     ("mvs_sweep_batch", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, C.c_float, C.c_float, _vp, _vp]),
     ("mvs_sweep_batch_async", _i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, C.c_float, C.c_float, _vp, _vp]),
@@ -669,14 +676,54 @@ class Context:
         self._check(self.lib.mvs_frame_store(self.h, int(capacity)))
         self._store_keep = {}
 
-    def frame_upload(self, slot, frame):
+    def frame_upload(self, slot, frame, lens=False):
+        """mvs_frame_upload; lens=True: mvs_frame_upload_lens (the frame goes through the context's lens on its way into the slot)"""
         f = _u8(frame, (self.H, self.W))
         self._store_keep[int(slot)] = f   # the copy is asynchronous: keep the array alive until the next synchronising call
-        self._check(self.lib.mvs_frame_upload(self.h, int(slot), f.ctypes.data_as(C.c_void_p)))
+        self._check((self.lib.mvs_frame_upload_lens if lens else self.lib.mvs_frame_upload)(self.h, int(slot), f.ctypes.data_as(C.c_void_p)))
 
-    def frame_upload_device(self, slot, frame_ptr):
-        """mvs_frame_upload_device: frame_ptr = device address of H*W u8 (stream-ordered)"""
-        self._check(self.lib.mvs_frame_upload_device(self.h, int(slot), C.c_void_p(int(frame_ptr))))
+    def frame_upload_device(self, slot, frame_ptr, lens=False):
+        """mvs_frame_upload_device (lens=True: mvs_frame_upload_lens_device): frame_ptr = device address of H*W u8 (stream-ordered)"""
+        self._check((self.lib.mvs_frame_upload_lens_device if lens else self.lib.mvs_frame_upload_device)(self.h, int(slot), C.c_void_p(int(frame_ptr))))
+
+    # ---- lens: distorted frames -> pinhole frames (include/mvs.h, DESIGN.md section 17) ---------
+    def set_lens(self, k, center=None):
+        """mvs_set_lens: k = up to three radial coefficients (None clears the lens); center = (center-x, center-y) in pixels, y from the
+        bottom as in the tracks files (None: the frame's centre)"""
+        if k is None:
+            self._check(self.lib.mvs_set_lens(self.h, None, 0.0, 0.0))
+            return
+        kk = np.zeros(3, np.float32)
+        k = np.asarray(k, np.float32).reshape(-1)
+        kk[:min(3, len(k))] = k[:3]
+        cx, cy = (self.W / 2.0, self.H / 2.0) if center is None else center
+        self._check(self.lib.mvs_set_lens(self.h, _ptr(kk, _fp), float(cx), float(cy)))
+
+    def lens(self):
+        """mvs_lens -> (k[3], (center-x, center-y)) or None when no lens is set"""
+        k = np.zeros(3, np.float32)
+        cx, cy = C.c_float(), C.c_float()
+        rc = self.lib.mvs_lens(self.h, _ptr(k, _fp), C.byref(cx), C.byref(cy))
+        if rc < 0:
+            self._check(rc)
+        return (k, (cx.value, cy.value)) if rc else None
+
+    def undistort(self, frame):
+        """mvs_undistort: one H x W u8 frame through the lens"""
+        f = _u8(frame, (self.H, self.W))
+        out = np.empty((self.H, self.W), np.uint8)
+        self._check(self.lib.mvs_undistort(self.h, _ptr(f, _u8p), _ptr(out, _u8p)))
+        return out
+
+    def undistort_device(self, src_ptr, dst_ptr, nframes=1):
+        """mvs_undistort_device: nframes tightly packed H*W u8 frames, device addresses, one launch (stream-ordered)"""
+        self._check(self.lib.mvs_undistort_device(self.h, C.c_void_p(int(src_ptr)), C.c_void_p(int(dst_ptr)), int(nframes)))
+
+    def undistort_map(self):
+        """mvs_undistort_map -> [H, W, 2] f32: the source position (x, y) of every output pixel, computed by the device"""
+        out = np.empty((self.H, self.W, 2), np.float32)
+        self._check(self.lib.mvs_undistort_map(self.h, _ptr(out, _fp)))
+        return out
 
     def sweep_handles(self, main_slot, main_cam, side_slots, side_cams, nplanes, z_lo=-1.0, z_hi=1.0, want_cost=False, out=None):
         """mvs_sweep_handles: one main view whose frames are slots of the frame store -> depth [H,W] (, cost)"""

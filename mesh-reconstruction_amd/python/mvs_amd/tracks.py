@@ -30,4 +30,7 @@ def load(name):
         "width": int(doc["clip"]["width"]), "height": int(doc["clip"]["height"]),
         "cameras": [c["projection"] for c in cams], "near": [c["near"] for c in cams], "far": [c["far"] for c in cams],
         "bundles": np.stack([t["bundle"].reshape(4) for t in doc["tracks"]]),
+        # the clip's lens: radial coefficients and the centre in pixels, y from the bottom (Context.set_lens takes them as they are)
+        "distortion": [float(k) for k in doc["clip"].get("distortion", [])],
+        "center_x": float(doc["clip"]["center-x"]), "center_y": float(doc["clip"]["center-y"]),
     }
