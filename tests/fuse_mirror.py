@@ -54,7 +54,8 @@ def _valid(z, cost, max_cost, t):
 
 def fuse(depths, costs, mats, ref, neighbours, min_consistent=2, max_reproj_px=1.0, max_rel_depth=0.01, max_cost=np.inf, dtype=np.float32):
     """depths / costs: slot -> [H, W] maps (costs may lack entries when max_cost is infinite); mats: slot -> (P, P^-1, centre).
-    Returns a dict: keep [H, W] bool, rows (N, 7) in ascending pixel index, and per-pixel intermediates (X, w, normal, agree, has_normal)."""
+    Returns a dict: keep [H, W] bool, rows (N, 7) in ascending pixel index, and per-pixel intermediates (X, w, normal, agree, has_normal, and
+    per neighbour the two quantities the thresholds are compared with)."""
     t = dtype
     H, W = depths[ref].shape
     halfW, halfH = t(W) * t(0.5), t(H) * t(0.5)
@@ -96,6 +97,7 @@ def fuse(depths, costs, mats, ref, neighbours, min_consistent=2, max_reproj_px=1
         Xc = (c[0], c[1], c[2])
         sx, sy, sz = c[0].copy(), c[1].copy(), c[2].copy()
         agree = np.zeros((H, W), np.int32)
+        tests = []   # per neighbour: (the sample reached both threshold tests, du^2 + dv^2, |sw - w| / w)
         colf, rowf = cols_i.astype(t), rows_i.astype(t)
         for j in neighbours:
             Pj, Pij, _ = [np.asarray(m, t) for m in mats[j]]
@@ -114,7 +116,9 @@ def fuse(depths, costs, mats, ref, neighbours, min_consistent=2, max_reproj_px=1
             ur = (_prow(P0, 0, Xj) / sw + t(1.0)) * halfW - t(0.5)
             vr = (t(1.0) - _prow(P0, 1, Xj) / sw) * halfH - t(0.5)
             du, dv = ur - colf, vr - rowf
-            a = vj & (sw > t(0.0)) & (du * du + dv * dv <= reproj2) & (np.abs(sw - c[3]) / c[3] <= max_rel)
+            d2, rel = du * du + dv * dv, np.abs(sw - c[3]) / c[3]
+            a = vj & (sw > t(0.0)) & (d2 <= reproj2) & (rel <= max_rel)
+            tests.append((vj & (sw > t(0.0)), d2, rel))
             sx = np.where(a, sx + Xj[0], sx)
             sy = np.where(a, sy + Xj[1], sy)
             sz = np.where(a, sz + Xj[2], sz)
@@ -123,4 +127,4 @@ def fuse(depths, costs, mats, ref, neighbours, min_consistent=2, max_reproj_px=1
         n = (agree + 1).astype(t)
         allrows = np.stack([sx / n, sy / n, sz / n, np.ones((H, W), t), nx, ny, nz], axis=-1)
     return {"keep": keep, "rows": allrows[keep].astype(t), "X": np.stack(Xc, -1), "w": c[3], "valid": ok, "has_normal": has_normal,
-            "normal": np.stack([nx, ny, nz], -1), "agree": agree}
+            "normal": np.stack([nx, ny, nz], -1), "agree": agree, "tests": tests}
