@@ -267,6 +267,40 @@ int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int spe
 int mvs_sweep_clean_report(mvs_ctx *ctx, int out[4]);
 void *mvs_sweep_clean_sizes_device(mvs_ctx *ctx);
 int mvs_sweep_clean_sizes_fetch(mvs_ctx *ctx, int32_t *sizes_hw);
+/* Windowed matching cost: gated box aggregation of the packed volume (csrc/window.hip; DESIGN.md section 18 is the arithmetic contract;
+ * exact integer arithmetic, bit-identical to tests/window_mirror.py).  A cell of the packed volume is the cost of ONE pixel; the windowed
+ * volume Wv holds, in the same cell format, the mean cost over a support window.  For pixel p and plane d the window is every pixel q of
+ * the frame with |q.row - p.row| <= radius and |q.col - p.col| <= radius whose guide value is close to p's, |G(q) - G(p)| <= tau (p
+ * itself always is; tau = 255 is the plain box and G is not read).  With S and N the sums of the members' cost sums and view counts (a
+ * member no view sees adds nothing) and n the pixel's own count, the cell of Wv is  n << CS | floor(S n / N)  (exact 64-bit integers), or
+ * 0 when n = 0: a hypothesis no view sees stays unseen.  The count field still is the pixel's own view count, the mean cost of the cell is
+ * the window's mean cost, so every reader of the packed volume works on Wv unchanged; radius 0 reproduces the volume cell for cell.
+ *   mvs_sweep_window reads the context's packed volume (its own or the caller's, either sampler), never modifies it, and writes every
+ * cell of Wv, a context-owned buffer of nplanes * H * W cells allocated by the first call.  guide_dev: H * W u8 on the context's GPU, NULL =
+ * the staged main image (mvs_sweep_set_main or the frame-store slot of mvs_sweep_handles).  Asynchronous on the context's stream, timed
+ * under MVS_K_ARGMIN.  MVS_WINDOW_SELECT: the same pass also rewrites the depth / cost / index maps with what mvs_sweep_argmin gives on Wv
+ * (lowest mean cost as an exact rational, ties to the lowest plane; -1 / MVS_BACKGROUND_DEPTH / +inf for a pixel nothing sees);
+ * MVS_WINDOW_REFINE (with SELECT): the depth map is what mvs_sweep_refine_depth then gives on Wv.  Both are bit-identical to the two-step
+ * form and cost no second read of the volume.
+ *   mvs_sweep_set_volume_source chooses the packed volume that mvs_sweep_argmin, mvs_sweep_refine_depth, mvs_sweep_aggregate (its matching
+ * cost C) and mvs_sweep_clean (rules 1 and 2) read: MVS_VOLUME_RAW (default) or MVS_VOLUME_WINDOWED (Wv).  Everything else --
+ * mvs_sweep_volume_device, mvs_sweep_fetch, mvs_sweep_use_volume, the sweep itself, the partial / combine pair, the communicator -- keeps
+ * meaning the raw volume.  The source survives sweeps and changes only through the setter.
+ * Errors: MVS_EINVAL for a NULL ctx, radius outside 0..4, tau outside 0..255, unknown flag bits, MVS_WINDOW_REFINE without
+ * MVS_WINDOW_SELECT, an unknown source, a NULL array for the fetch; MVS_ESTATE without planes or a packed volume of nplanes * H * W cells,
+ * for tau < 255 (and radius > 0) with a NULL guide and no staged main image, for mvs_sweep_window_fetch before the first window, and for
+ * any of the four readers under MVS_VOLUME_WINDOWED while there is no Wv of the current plane count; MVS_ENOMEM.  After an error nothing
+ * is written and the context stays usable.  mvs_sweep_windowed_device: Wv and its size (NULL before the first call);
+ * mvs_sweep_window_fetch synchronises and downloads Wv (diagnostic). */
+#define MVS_WINDOW_SELECT 1u
+#define MVS_WINDOW_REFINE 2u
+int mvs_sweep_window(mvs_ctx *ctx, int radius, int tau, const void *guide_dev, unsigned flags);
+void *mvs_sweep_windowed_device(mvs_ctx *ctx, size_t *bytes);
+int mvs_sweep_window_fetch(mvs_ctx *ctx, uint32_t *cells_dhw);
+#define MVS_VOLUME_RAW 0
+#define MVS_VOLUME_WINDOWED 1
+int mvs_sweep_set_volume_source(mvs_ctx *ctx, int source);
+int mvs_sweep_volume_source(const mvs_ctx *ctx);
 /* The same selection in two steps, for a view-sharded job that REDUCE-SCATTERS the packed volume instead of all-reducing it
  * (half the bytes over xGMI): rank r owns the summed cells of planes [plane_first, plane_first + plane_count) in
  * `volume_slice_dev` ([plane_count][H][W] u32) and selects a partial best per pixel over them -- `partial_out_dev` receives

@@ -335,13 +335,16 @@ int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, u
     if ((long long)paths * ((long long)cost_cap + p2) > 65535)
         return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: paths (cost_cap + p2) = %lld does not fit 16 bits", (long long)paths * ((long long)cost_cap + p2));
     if (flags & ~MVS_AGGREGATE_REFINE) return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: unknown flag bits 0x%x", flags & ~MVS_AGGREGATE_REFINE);
-    if (!ctx->have_planes || !ctx->volume)
+    const uint32_t *vol;
+    size_t vol_bytes;
+    if (int rc = reader_volume(ctx, "mvs_sweep_aggregate", vol, vol_bytes)) return rc;
+    if (!ctx->have_planes || !vol)
         return fail(ctx, MVS_ESTATE, "mvs_sweep_aggregate: no cost volume (run mvs_sweep_run with MVS_SWEEP_VOLUME)");
     const int W = ctx->W, H = ctx->H, D = ctx->D;
     if (D < 2 || D > kAggMaxPlanes) return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: %d planes outside 2..%d", D, kAggMaxPlanes);
     const size_t P = (size_t)W * H, N = P * (size_t)D;
-    if (ctx->volume_bytes < N * sizeof(uint32_t))
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: the volume is %zu bytes, %d planes need %zu", ctx->volume_bytes, D, N * sizeof(uint32_t));
+    if (vol_bytes < N * sizeof(uint32_t))
+        return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: the volume is %zu bytes, %d planes need %zu", vol_bytes, D, N * sizeof(uint32_t));
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
@@ -355,9 +358,9 @@ int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, u
     ProfileScope ps(ctx, MVS_K_ARGMIN);
     const unsigned cblocks = (unsigned)((N + 255) / 256);
     if (fx)
-        agg_cost_kernel<CS_FIXED><<<cblocks, 256, 0, ctx->stream>>>(ctx->volume, N, (uint32_t)cost_cap, C);
+        agg_cost_kernel<CS_FIXED><<<cblocks, 256, 0, ctx->stream>>>(vol, N, (uint32_t)cost_cap, C);
     else
-        agg_cost_kernel<CS_EXACT><<<cblocks, 256, 0, ctx->stream>>>(ctx->volume, N, (uint32_t)cost_cap, C);
+        agg_cost_kernel<CS_EXACT><<<cblocks, 256, 0, ctx->stream>>>(vol, N, (uint32_t)cost_cap, C);
     MVS_HIP(ctx, hipGetLastError());
     // paths (0, +1) and (0, -1): the launch that stores S
     if (D <= 64)
@@ -381,10 +384,10 @@ int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, u
     const int refine = (flags & MVS_AGGREGATE_REFINE) ? 1 : 0;
     const unsigned sblocks = (unsigned)((P + 255) / 256);
     if (fx)
-        agg_select_kernel<CS_FIXED><<<sblocks, 256, 0, ctx->stream>>>(S, ctx->volume, P, D, (const float *)ctx->ztab.ptr, cost_div, refine, (float *)ctx->depth.ptr,
+        agg_select_kernel<CS_FIXED><<<sblocks, 256, 0, ctx->stream>>>(S, vol, P, D, (const float *)ctx->ztab.ptr, cost_div, refine, (float *)ctx->depth.ptr,
                                                                       (float *)ctx->cost.ptr, (int *)ctx->index.ptr);
     else
-        agg_select_kernel<CS_EXACT><<<sblocks, 256, 0, ctx->stream>>>(S, ctx->volume, P, D, (const float *)ctx->ztab.ptr, cost_div, refine, (float *)ctx->depth.ptr,
+        agg_select_kernel<CS_EXACT><<<sblocks, 256, 0, ctx->stream>>>(S, vol, P, D, (const float *)ctx->ztab.ptr, cost_div, refine, (float *)ctx->depth.ptr,
                                                                       (float *)ctx->cost.ptr, (int *)ctx->index.ptr);
     MVS_HIP(ctx, hipGetLastError());
     ctx->agg_planes = D;

@@ -283,7 +283,10 @@ int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int spe
     const size_t P = (size_t)W * H;
     if (P > (size_t)INT_MAX) return fail(ctx, MVS_EINVAL, "mvs_sweep_clean: %zu pixels do not fit the 32-bit labels", P);
     const bool agg = (flags & MVS_CLEAN_SCORES_AGGREGATED) != 0;
-    const bool have_volume = ctx->have_planes && ctx->volume && ctx->volume_bytes >= P * (size_t)D * sizeof(uint32_t);
+    const uint32_t *vol;
+    size_t vol_bytes;
+    if (int rc = reader_volume(ctx, "mvs_sweep_clean", vol, vol_bytes)) return rc;
+    const bool have_volume = ctx->have_planes && vol && vol_bytes >= P * (size_t)D * sizeof(uint32_t);
     // min_views 1 rejects a selected cell that no view sees; the library selects none, so without a volume there is nothing to test
     const bool rule1 = min_views >= 2 || (min_views == 1 && have_volume), rule2 = uniqueness_percent > 0, rule3 = speckle_min_size > 0;
     if ((rule1 || rule2) && !have_volume)
@@ -312,13 +315,13 @@ int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int spe
         const bool fx = ctx->sampler == MVS_SAMPLER_FIXED;
         const uint32_t mv = (uint32_t)min_views, u = (uint32_t)uniqueness_percent;
         if (fx && agg)
-            clean_rules_kernel<CS_FIXED, true><<<pblocks, 256, 0, ctx->stream>>>(S, ctx->volume, P, D, rule1, mv, u, depth, cost, index, counters);
+            clean_rules_kernel<CS_FIXED, true><<<pblocks, 256, 0, ctx->stream>>>(S, vol, P, D, rule1, mv, u, depth, cost, index, counters);
         else if (fx)
-            clean_rules_kernel<CS_FIXED, false><<<pblocks, 256, 0, ctx->stream>>>(nullptr, ctx->volume, P, D, rule1, mv, u, depth, cost, index, counters);
+            clean_rules_kernel<CS_FIXED, false><<<pblocks, 256, 0, ctx->stream>>>(nullptr, vol, P, D, rule1, mv, u, depth, cost, index, counters);
         else if (agg)
-            clean_rules_kernel<CS_EXACT, true><<<pblocks, 256, 0, ctx->stream>>>(S, ctx->volume, P, D, rule1, mv, u, depth, cost, index, counters);
+            clean_rules_kernel<CS_EXACT, true><<<pblocks, 256, 0, ctx->stream>>>(S, vol, P, D, rule1, mv, u, depth, cost, index, counters);
         else
-            clean_rules_kernel<CS_EXACT, false><<<pblocks, 256, 0, ctx->stream>>>(nullptr, ctx->volume, P, D, rule1, mv, u, depth, cost, index, counters);
+            clean_rules_kernel<CS_EXACT, false><<<pblocks, 256, 0, ctx->stream>>>(nullptr, vol, P, D, rule1, mv, u, depth, cost, index, counters);
     } else {
         clean_count_kernel<<<pblocks, 256, 0, ctx->stream>>>(index, P, counters);
     }

@@ -197,6 +197,11 @@ struct mvs_ctx {
     // Allocated by the first call that needs them.
     mvs::DevBuf clean_labels, clean_sizes, clean_counters;
     bool clean_done = false, clean_have_sizes = false;
+    // windowed matching cost (window.hip: mvs_sweep_window): Wv, packed cells [D][H][W] u32, allocated by the first call; win_planes = D of
+    // the last call (0: no Wv yet); volume_source = which packed volume argmin / refine / aggregate / clean read (mvs::reader_volume)
+    mvs::DevBuf win_vol;
+    int win_planes = 0;
+    int volume_source = MVS_VOLUME_RAW;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;
@@ -241,6 +246,10 @@ int tsdf_ensure_field(mvs_ctx *ctx, int min_obs);
 int tsdf_ensure_appearance(mvs_ctx *ctx);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
+
+// window.hip: the packed volume the readers of mvs_sweep_set_volume_source read -- the raw volume as the context holds it (pointer and size
+// may be null / short: the reader's own checks apply, as before), or Wv; MVS_ESTATE under MVS_VOLUME_WINDOWED without a Wv of the current planes
+int reader_volume(mvs_ctx *ctx, const char *who, const uint32_t *&vol, size_t &bytes);
 
 // a writer of every row of ctx->index has been launched over the current planes (mvs_ctx::sel_planes)
 inline void note_full_selection(mvs_ctx *ctx)

@@ -1041,14 +1041,19 @@ static void launch_argmin(mvs_ctx *ctx, const uint32_t *vol, size_t P, int D, co
 int mvs_sweep_argmin(mvs_ctx *ctx)
 {
     if (!ctx) return MVS_EINVAL;
-    if (!ctx->have_planes || !ctx->volume)
+    const uint32_t *vol;
+    size_t vol_bytes;
+    int rc = reader_volume(ctx, "mvs_sweep_argmin", vol, vol_bytes);   // refuses before anything is allocated
+    if (rc) return rc;
+    const bool raw = ctx->volume_source == MVS_VOLUME_RAW;
+    if (raw && (!ctx->have_planes || !ctx->volume))
         return fail(ctx, MVS_ESTATE, "mvs_sweep_argmin: no cost volume (run mvs_sweep_run with MVS_SWEEP_VOLUME)");
     MVS_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_outputs(ctx, true);
-    if (rc) return rc;
+    if ((rc = ensure_outputs(ctx, raw))) return rc;
+    if (raw) vol = ctx->volume;   // (ensure_outputs may have re-made the context's own)
     const size_t P = (size_t)ctx->W * ctx->H;
     ProfileScope ps(ctx, MVS_K_ARGMIN);
-    launch_argmin(ctx, ctx->volume, P, ctx->D, (const float *)ctx->ztab.ptr, (float *)ctx->depth.ptr, (float *)ctx->cost.ptr, (int *)ctx->index.ptr,
+    launch_argmin(ctx, vol, P, ctx->D, (const float *)ctx->ztab.ptr, (float *)ctx->depth.ptr, (float *)ctx->cost.ptr, (int *)ctx->index.ptr,
                   nullptr, 0);
     MVS_HIP(ctx, hipGetLastError());
     note_full_selection(ctx);
@@ -1058,22 +1063,25 @@ int mvs_sweep_argmin(mvs_ctx *ctx)
 int mvs_sweep_refine_depth(mvs_ctx *ctx)
 {
     if (!ctx) return MVS_EINVAL;
-    if (!ctx->have_planes || !ctx->volume || !ctx->index.ptr || !ctx->sel_planes)
+    const uint32_t *vol;
+    size_t vol_bytes;
+    if (int rc = reader_volume(ctx, "mvs_sweep_refine_depth", vol, vol_bytes)) return rc;
+    if (!ctx->have_planes || !vol || !ctx->index.ptr || !ctx->sel_planes)
         return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: needs the packed volume and a depth selection (MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN, or mvs_sweep_argmin)");
     // the kernel reads z[index] and the cells of planes index - 1 .. index + 1: the index map must be one over the current planes ...
     if (ctx->sel_planes != ctx->D)
         return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: the depth selection was made over %d planes, the context now has %d (select again)", ctx->sel_planes, ctx->D);
     // ... and the volume must hold them (ensure_outputs and mvs_sweep_aggregate refuse the same)
     const size_t P = (size_t)ctx->W * ctx->H, need = P * (size_t)ctx->D * sizeof(uint32_t);
-    if (ctx->volume_bytes < need) {
-        if (ctx->volume_external) return fail(ctx, MVS_EINVAL, "mvs_sweep_refine_depth: caller volume is %zu bytes, %d planes need %zu", ctx->volume_bytes, ctx->D, need);
-        return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: the context's volume is %zu bytes, %d planes need %zu (mvs_sweep_run with MVS_SWEEP_VOLUME)", ctx->volume_bytes, ctx->D, need);
+    if (vol_bytes < need) {
+        if (ctx->volume_external) return fail(ctx, MVS_EINVAL, "mvs_sweep_refine_depth: caller volume is %zu bytes, %d planes need %zu", vol_bytes, ctx->D, need);
+        return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: the context's volume is %zu bytes, %d planes need %zu (mvs_sweep_run with MVS_SWEEP_VOLUME)", vol_bytes, ctx->D, need);
     }
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->sampler == MVS_SAMPLER_FIXED)
-        refine_depth<CS_FIXED><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(ctx->volume, P, ctx->D, (const float *)ctx->ztab.ptr, (const int *)ctx->index.ptr, (float *)ctx->depth.ptr);
+        refine_depth<CS_FIXED><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(vol, P, ctx->D, (const float *)ctx->ztab.ptr, (const int *)ctx->index.ptr, (float *)ctx->depth.ptr);
     else
-        refine_depth<CS_EXACT><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(ctx->volume, P, ctx->D, (const float *)ctx->ztab.ptr, (const int *)ctx->index.ptr, (float *)ctx->depth.ptr);
+        refine_depth<CS_EXACT><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(vol, P, ctx->D, (const float *)ctx->ztab.ptr, (const int *)ctx->index.ptr, (float *)ctx->depth.ptr);
     MVS_HIP(ctx, hipGetLastError());
     return MVS_OK;
 }

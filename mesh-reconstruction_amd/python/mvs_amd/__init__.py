@@ -23,6 +23,9 @@ MVS_SWEEP_FORCE_GENERIC = 4
 MVS_SWEEP_NO_RECT = 8
 MVS_AGGREGATE_REFINE = 1
 MVS_CLEAN_SCORES_AGGREGATED = 1
+MVS_WINDOW_SELECT, MVS_WINDOW_REFINE = 1, 2
+MVS_VOLUME_RAW, MVS_VOLUME_WINDOWED = 0, 1
+VOLUME_SOURCES = {"raw": MVS_VOLUME_RAW, "windowed": MVS_VOLUME_WINDOWED}
 MVS_SHARD_ROWS, MVS_SHARD_VIEWS, MVS_SHARD_VIEWS_SCATTER = 0, 1, 2
 SHARD_MODES = {"rows": 0, "views": 1, "views_scatter": 2}
 MVS_SAMPLER_FIXED, MVS_SAMPLER_EXACT_F32 = 0, 1
@@ -121,6 +124,11 @@ ABI = [
     ("mvs_sweep_clean_report", _i, [_vp, C.POINTER(_i)]),
     ("mvs_sweep_clean_sizes_device", _vp, [_vp]),
     ("mvs_sweep_clean_sizes_fetch", _i, [_vp, _i32p]),
+    ("mvs_sweep_window", _i, [_vp, _i, _i, _vp, C.c_uint]),
+    ("mvs_sweep_windowed_device", _vp, [_vp, C.POINTER(_sz)]),
+    ("mvs_sweep_window_fetch", _i, [_vp, _u32p]),
+    ("mvs_sweep_set_volume_source", _i, [_vp, _i]),
+    ("mvs_sweep_volume_source", _i, [_vp]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
     ("mvs_sweep_combine_partials", _i, [_vp, _vp, _i]),
     ("mvs_sweep_volume_device", _vp, [_vp, C.POINTER(_sz)]),
@@ -627,6 +635,12 @@ class Context:
         self._check(self.lib.mvs_sweep_set_planes(self.h, int(nplanes), float(z_lo), float(z_hi)))
         self.D = int(nplanes)
 
+    def sweep_set_main(self, main_cam, main_img):
+        """mvs_sweep_set_main alone: the main camera and its H*W u8 image (the default guide of sweep_window)"""
+        cam = _f32(main_cam, (4, 4))
+        img = _u8(main_img, (self.H, self.W))
+        self._check(self.lib.mvs_sweep_set_main(self.h, _ptr(cam, _fp), _ptr(img, _u8p)))
+
     def sweep_set_main_device(self, main_cam, main_ptr):
         """mvs_sweep_set_main_device: main_ptr = address of H*W u8 in the memory of the context's GPU (e.g. tensor.data_ptr()); stream-ordered"""
         cam = _f32(main_cam, (4, 4))
@@ -1027,6 +1041,41 @@ class Context:
         sizes = np.empty((self.H, self.W), np.int32)
         self._check(self.lib.mvs_sweep_clean_sizes_fetch(self.h, _ptr(sizes, _i32p)))
         return sizes
+
+    def sweep_window(self, radius=2, tau=255, guide_ptr=None, select=True, refine=False):
+        """mvs_sweep_window: the windowed volume Wv of the packed volume -- per cell the mean cost over the (2 radius + 1)^2 window, taking
+        only the neighbours whose guide value is within `tau` of the pixel's (guide_ptr: device address of H*W uint8, None = the staged
+        main image; tau 255 = plain box); `select` also rewrites the depth / cost / index maps from Wv, `refine` with the parabola
+        (asynchronous, stream-ordered)"""
+        flags = (MVS_WINDOW_SELECT if select else 0) | (MVS_WINDOW_REFINE if refine else 0)
+        self._check(self.lib.mvs_sweep_window(self.h, int(radius), int(tau), C.c_void_p(guide_ptr) if guide_ptr else None, flags))
+
+    def sweep_window_fetch(self):
+        """mvs_sweep_window_fetch -> Wv (D, H, W) uint32 of the last sweep_window (synchronises)"""
+        n = _sz(0)
+        self.lib.mvs_sweep_windowed_device(self.h, C.byref(n))
+        if not n.value:   # no window yet: the library's answer (MVS_ESTATE)
+            self._check(self.lib.mvs_sweep_window_fetch(self.h, (C.c_uint32 * 1)()))
+            raise MvsError("sweep_window_fetch: no windowed volume yet")
+        cells = np.empty((n.value // (4 * self.H * self.W), self.H, self.W), np.uint32)
+        self._check(self.lib.mvs_sweep_window_fetch(self.h, _ptr(cells, _u32p)))
+        return cells
+
+    def sweep_windowed_device(self):
+        """(device address, bytes) of Wv, [D][H][W] uint32; raises before the first sweep_window"""
+        n = _sz(0)
+        p = self.lib.mvs_sweep_windowed_device(self.h, C.byref(n))
+        if not p:
+            raise MvsError("no windowed volume yet (sweep_window first)")
+        return p, n.value
+
+    def set_volume_source(self, source):
+        """mvs_sweep_set_volume_source: "raw" / "windowed" (or the constants): the packed volume sweep_argmin, sweep_refine_depth,
+        sweep_aggregate and sweep_clean read"""
+        self._check(self.lib.mvs_sweep_set_volume_source(self.h, VOLUME_SOURCES.get(source, source)))
+
+    def volume_source(self):
+        return self.lib.mvs_sweep_volume_source(self.h)
 
     def sweep_argmin_partial(self, volume_slice_ptr, plane_first, plane_count, partial_out_ptr):
         self._check(self.lib.mvs_sweep_argmin_partial(self.h, C.c_void_p(volume_slice_ptr), int(plane_first), int(plane_count),
