@@ -301,6 +301,49 @@ int mvs_sweep_window_fetch(mvs_ctx *ctx, uint32_t *cells_dhw);
 #define MVS_VOLUME_WINDOWED 1
 int mvs_sweep_set_volume_source(mvs_ctx *ctx, int source);
 int mvs_sweep_volume_source(const mvs_ctx *ctx);
+/* Band sweep: the planes in a per-pixel band around a depth prior (csrc/band.hip; DESIGN.md section 19 is the arithmetic contract; all
+ * f32, one rounding per operation, bit-identical to tests/band_mirror.py).  Fixed sampler only.  Plane d of pixel p is
+ * z = prior(p) + delta_d, so the planes are spent where a coarser result -- a coarse sweep's refined map, mvs_depth of a proxy mesh,
+ * mvs_tsdf_raycast -- says the surface is.
+ *   1. Prior: prior_dev is H * W f32 on the context's GPU in the library's depth convention for the main camera.  A pixel has a prior when
+ *      -1 < z0 < 1 (NaN has none).  The call copies the map into a context-owned buffer (device to device, on the context's stream;
+ *      allocated by the first call), so prior_dev may be mvs_sweep_depth_device(ctx) itself.
+ *   2. Offsets: delta is the context's plane table, mvs_sweep_set_planes(ctx, D, lo, hi) with -1 < lo < hi < 1, typically (-hb, +hb).
+ *      z_d(p) = z0 + delta_d is one f32 add; plane d of pixel p is live when -1 < z_d(p) < 1.
+ *   3. Cell: for a pixel with a prior and a live plane, the sum of (1 << 24) + |dot - 255 I_main| over the views of
+ *      [view_first, view_first + view_count) that the fixed sampler's sample at (xn, yn, z_d(p)) finds in frame -- the sample of
+ *      mvs_sweep_run, bit for bit; otherwise 0.  Layout [D][H][W] u32 in the context's packed volume (its own or the caller's); as in
+ *      mvs_sweep_run the cells are the sums of the listed views, not added to what was there.
+ *   4. Selection: MVS_SWEEP_FUSED_ARGMIN gives what mvs_sweep_argmin gives on that volume with the table delta: lowest mean cost as an
+ *      exact rational, ties to the lowest plane, cost and index as usual, -1 / MVS_BACKGROUND_DEPTH / +inf for a pixel with no seen cell.
+ *      THE DEPTH MAP HOLDS OFFSETS: delta[index], not depths, after a band run and after every re-selection on its volume
+ *      (mvs_sweep_argmin, _refine_depth, _window, _aggregate, _clean: all work in the index domain and run unchanged), until resolved.
+ *      An offset never is 1.0 for a selected pixel (hi < 1, and refinement moves at most half a step).  A band run without
+ *      MVS_SWEEP_FUSED_ARGMIN leaves the context WITHOUT a depth selection (the index map is not one on this volume) until
+ *      mvs_sweep_argmin or another selecting call.
+ *   5. Resolve: mvs_sweep_band_resolve writes band_depth, a separate context-owned H * W f32 map: for a pixel with index >= 0,
+ *      z = z0 + depth(p) in one add, written if -1 < z < 1, else MVS_BACKGROUND_DEPTH; MVS_BACKGROUND_DEPTH for index < 0.  The depth /
+ *      cost / index maps are not modified, so the call is idempotent and can follow any re-selection.  The same kernel counts, for
+ *      mvs_sweep_band_report: out[0] pixels with a prior, [1] pixels with an index, [2] pixels whose index is 0 or D - 1 ("band edge":
+ *      the sign of a band too narrow for its prior), [3] pixels emptied by the range test.
+ * mvs_sweep_run_band works on the context's staged state however it got there (mvs_sweep_set_main / _views, host or device forms, or the
+ * slots left staged by mvs_sweep_handles); flags: MVS_SWEEP_VOLUME and / or MVS_SWEEP_FUSED_ARGMIN.  It is asynchronous on the context's
+ * stream and timed under MVS_K_SWEEP; mvs_sweep_band_resolve is asynchronous and timed under MVS_K_ARGMIN; mvs_sweep_band_fetch and
+ * mvs_sweep_band_report synchronise.  mvs_sweep_band_depth_device: band_depth (NULL before the first resolve), e.g. for
+ * mvs_depth_upload_device(ctx, slot, cam, mvs_sweep_band_depth_device(ctx), mvs_sweep_cost_device(ctx)); mvs_sweep_band_prior_device: the
+ * context's copy of the prior (NULL before the first band run).  A wrong prior confines the band to the wrong place: outliers of the
+ * prior stay outliers.
+ * Errors: MVS_EINVAL for a NULL ctx, prior or array, a view range outside 0..V, flags that select neither output, unknown flag bits
+ * (MVS_SWEEP_FORCE_GENERIC and MVS_SWEEP_NO_RECT are unknown here); MVS_ESTATE without main view, views or planes, for a plane table not
+ * inside (-1, 1), for the exact sampler; MVS_ESTATE from resolve, fetch and report before a band run, after an ordinary mvs_sweep_run*
+ * since, without a depth selection over the current plane count, when the plane count has changed since the band run, and from fetch and
+ * report before the band run's resolve; MVS_ENOMEM.  After an error nothing is written and the context stays usable. */
+int mvs_sweep_run_band(mvs_ctx *ctx, int view_first, int view_count, const void *prior_dev, unsigned flags);
+int mvs_sweep_band_resolve(mvs_ctx *ctx);
+void *mvs_sweep_band_depth_device(mvs_ctx *ctx);
+void *mvs_sweep_band_prior_device(mvs_ctx *ctx);
+int mvs_sweep_band_fetch(mvs_ctx *ctx, float *depth_hw);
+int mvs_sweep_band_report(mvs_ctx *ctx, int out[4]);
 /* The same selection in two steps, for a view-sharded job that REDUCE-SCATTERS the packed volume instead of all-reducing it
  * (half the bytes over xGMI): rank r owns the summed cells of planes [plane_first, plane_first + plane_count) in
  * `volume_slice_dev` ([plane_count][H][W] u32) and selects a partial best per pixel over them -- `partial_out_dev` receives

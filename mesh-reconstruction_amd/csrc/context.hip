@@ -275,7 +275,7 @@ void mvs_destroy(mvs_ctx *ctx)
                       &ctx->r_mips, &ctx->flow_batch_arena, &ctx->rect_tab, &ctx->r_tris_main, &ctx->store_raw, &ctx->store_quads, &ctx->batch_slot[0].buf, &ctx->batch_slot[1].buf, &ctx->frame_ptrs, &ctx->view_slots, &ctx->xrect_tab, &ctx->sep_tab,
                       &ctx->dstore_depth, &ctx->dstore_cost, &ctx->fuse_rows, &ctx->fuse_counts, &ctx->fuse_scan,
                       &ctx->tsdf_vol, &ctx->tsdf_wmaps, &ctx->tsdf_work, &ctx->tsdf_bricks, &ctx->ray_depth, &ctx->ray_normals, &ctx->agg_cost, &ctx->agg_sum,
-                      &ctx->clean_labels, &ctx->clean_sizes, &ctx->clean_counters, &ctx->win_vol,
+                      &ctx->clean_labels, &ctx->clean_sizes, &ctx->clean_counters, &ctx->win_vol, &ctx->band_prior, &ctx->band_depth, &ctx->band_counters,
                       &ctx->tsdf_app, &ctx->shade_map, &ctx->app_points, &ctx->lens_stage};
     for (DevBuf *b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);

@@ -202,6 +202,12 @@ struct mvs_ctx {
     mvs::DevBuf win_vol;
     int win_planes = 0;
     int volume_source = MVS_VOLUME_RAW;
+    // band sweep (band.hip: mvs_sweep_run_band): the context's copy of the prior, the absolute depths of the last mvs_sweep_band_resolve and
+    // its report's four counters, H*W f32 / H*W f32 / 4 i32, each allocated by the first call that needs it.  band_planes = D of the last
+    // band run while the maps are still its (0: none yet, or an ordinary sweep ran since); band_resolved: band_depth belongs to that run
+    mvs::DevBuf band_prior, band_depth, band_counters;
+    int band_planes = 0;
+    bool band_resolved = false;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

@@ -1016,6 +1016,7 @@ static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags)
     int rc = ensure_outputs(ctx, f.vol);
     if (rc) return rc;
     if (r.row_count <= 0 || r.plane_count <= 0) return MVS_OK;  // empty band or empty plane group: nothing to compute
+    ctx->band_planes = 0;  // the volume and the maps stop being a band run's (band.hip: mvs_sweep_band_resolve refuses from here on)
     rc = ctx->sampler == MVS_SAMPLER_FIXED ? sweep_run_fixed(ctx, r, f) : sweep_run_exact(ctx, r, f);
     if (rc == MVS_OK && f.fused) note_selection(ctx, r.row_first, r.row_first + r.row_count);
     return rc;

@@ -129,6 +129,12 @@ ABI = [
     ("mvs_sweep_window_fetch", _i, [_vp, _u32p]),
     ("mvs_sweep_set_volume_source", _i, [_vp, _i]),
     ("mvs_sweep_volume_source", _i, [_vp]),
+    ("mvs_sweep_run_band", _i, [_vp, _i, _i, _vp, C.c_uint]),
+    ("mvs_sweep_band_resolve", _i, [_vp]),
+    ("mvs_sweep_band_depth_device", _vp, [_vp]),
+    ("mvs_sweep_band_prior_device", _vp, [_vp]),
+    ("mvs_sweep_band_fetch", _i, [_vp, _fp]),
+    ("mvs_sweep_band_report", _i, [_vp, C.POINTER(_i)]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
     ("mvs_sweep_combine_partials", _i, [_vp, _vp, _i]),
     ("mvs_sweep_volume_device", _vp, [_vp, C.POINTER(_sz)]),
@@ -408,6 +414,24 @@ def pinned_array(shape, dtype):
     import weakref
     weakref.finalize(buf, lib.mvs_host_free, ptr)
     return arr
+
+
+def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, fetch=True):
+    """Two-level sweep on the inputs staged on `ctx` (main view and side views; fixed sampler): `coarse_planes` planes over [z_lo, z_hi],
+    refined; then `band_planes` planes within +- band_steps coarse steps of that map (mvs_sweep_run_band with the context's own depth map
+    as the prior), refined and resolved.  Pure composition of Context calls -> the absolute depth map (H, W) float32 (fetch=False: None,
+    the map stays on the device: sweep_band_pointers()[0]); the context is left
+    with the band's plane table, volume and maps (the depth map holds offsets), and sweep_band_report() tells how the band fared.  A wrong
+    coarse depth confines the band to the wrong place: this lowers the median error, not the outliers."""
+    flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
+    ctx.sweep_set_planes(coarse_planes, z_lo, z_hi)
+    ctx.sweep_run(0, None, flags)
+    ctx.sweep_refine_depth()
+    hb = float(np.float32(band_steps * (float(z_hi) - float(z_lo)) / coarse_planes))
+    ctx.sweep_set_planes(band_planes, -hb, hb)
+    ctx.sweep_run_band(ctx.sweep_result_pointers()[0], 0, None, flags)
+    ctx.sweep_refine_depth()
+    return ctx.sweep_band_resolve(fetch=fetch)
 
 
 class Comm:
@@ -1076,6 +1100,35 @@ class Context:
 
     def volume_source(self):
         return self.lib.mvs_sweep_volume_source(self.h)
+
+    def sweep_run_band(self, prior_ptr, view_first=0, view_count=None, flags=MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN):
+        """mvs_sweep_run_band: the fixed sampler's sweep with plane d of pixel p at prior(p) + delta_d, delta = the staged plane table
+        (sweep_set_planes(D, -hb, +hb)); prior_ptr: device address of H*W float32, e.g. sweep_result_pointers()[0].  The depth map holds
+        OFFSETS until sweep_band_resolve (asynchronous, stream-ordered)"""
+        if view_count is None:
+            view_count = self.V - view_first
+        self._check(self.lib.mvs_sweep_run_band(self.h, int(view_first), int(view_count), C.c_void_p(int(prior_ptr)) if prior_ptr else None, int(flags)))
+
+    def sweep_band_resolve(self, fetch=True):
+        """mvs_sweep_band_resolve: prior + selected offset -> the absolute depth map band_depth (the depth / cost / index maps stay);
+        fetch: -> (H, W) float32 (synchronises), else None (asynchronous)"""
+        self._check(self.lib.mvs_sweep_band_resolve(self.h))
+        if not fetch:
+            return None
+        depth = np.empty((self.H, self.W), np.float32)
+        self._check(self.lib.mvs_sweep_band_fetch(self.h, _ptr(depth, _fp)))
+        return depth
+
+    def sweep_band_report(self):
+        """mvs_sweep_band_report -> [pixels with a prior, with an index, with index 0 or D - 1, emptied by the range test] of the last
+        sweep_band_resolve (synchronises)"""
+        out = (C.c_int * 4)()
+        self._check(self.lib.mvs_sweep_band_report(self.h, out))
+        return list(out)
+
+    def sweep_band_pointers(self):
+        """(device address of band_depth, of the context's copy of the prior); 0 before the first resolve / band run"""
+        return self.lib.mvs_sweep_band_depth_device(self.h) or 0, self.lib.mvs_sweep_band_prior_device(self.h) or 0
 
     def sweep_argmin_partial(self, volume_slice_ptr, plane_first, plane_count, partial_out_ptr):
         self._check(self.lib.mvs_sweep_argmin_partial(self.h, C.c_void_p(volume_slice_ptr), int(plane_first), int(plane_count),
