@@ -344,6 +344,45 @@ void *mvs_sweep_band_depth_device(mvs_ctx *ctx);
 void *mvs_sweep_band_prior_device(mvs_ctx *ctx);
 int mvs_sweep_band_fetch(mvs_ctx *ctx, float *depth_hw);
 int mvs_sweep_band_report(mvs_ctx *ctx, int out[4]);
+/* Resolution pyramid: a half-resolution coarse level for the band sweep (csrc/pyramid.hip; DESIGN.md section 20 is the contract;
+ * bit-identical to tests/pyramid_mirror.py).  The levels are separate contexts on the SAME GPU: `fine` is W x H with W and H even,
+ * `coarse` exactly (W/2) x (H/2).  The cameras are NDC matrices and the centre of a coarse pixel is the mean of the centres of its four
+ * fine pixels, so the same 4 x 4 matrices serve every level.  Fixed sampler.  Opt-in: a context that never calls these allocates nothing
+ * and behaves bit for bit as before.
+ *   Rule D (frames, exact integers): coarse[r][c] = (f[2r][2c] + f[2r][2c+1] + f[2r+1][2c] + f[2r+1][2c+1] + 2) >> 2.
+ *   Rule U (prior, f32, one rounding per operation, no contraction): for fine pixel (r, c), r0 = (r - 1) >> 1 (arithmetic shift),
+ *      r1 = r0 + 1, both clamped to [0, H/2 - 1]; row weights wy0 = (r & 1) ? 3 : 1, wy1 = 4 - wy0; columns alike.  The four taps, in the
+ *      order (r0,c0), (r0,c1), (r1,c0), (r1,c1), have the integer weights w = wy * wx (a clamped tap keeps its weight).  A tap is valid
+ *      when -1 < z < 1 (false for NaN).  With tau < 255 a valid tap is a member when |Gc(tap) - Gf(r, c)| <= tau, Gc and Gf being the
+ *      staged main images of the coarse and the fine context; if no valid tap is a member, every valid tap is one.  With tau = 255 the
+ *      guides are not read and every valid tap is a member.  num = the sum of (float)w * z over the members in tap order, starting at
+ *      the first member's product; z = num / (float)(sum of the members' w); the output is z if -1 < z < 1, else MVS_BACKGROUND_DEPTH,
+ *      and MVS_BACKGROUND_DEPTH without a valid tap.
+ *   mvs_pyramid_downsample_device(fine, src, dst, n)   rule D on n (1..65535) tightly packed W x H frames on fine's GPU into n tightly
+ *      packed (W/2) x (H/2) frames, one launch, asynchronous on fine's stream; MVS_EINVAL when the two ranges overlap.
+ *   mvs_pyramid_stage(fine, coarse)   stages on `coarse` the rule-D copy of what is staged on `fine` -- the main image as the sweep reads
+ *      it, every side view, the same cameras -- however it got there: mvs_sweep_set_main / _views, the _device forms, mvs_sweep, the slots
+ *      left staged by mvs_sweep_handles, or an earlier mvs_pyramid_stage (full -> 1/2 -> 1/4 works).  The frames go into a coarse-owned
+ *      buffer of (V + 1)(W/2)(H/2) bytes allocated by the first call; the call then is mvs_sweep_set_main_device +
+ *      mvs_sweep_set_views_device on `coarse` with those frames, so the coarse context's state is byte for byte that of those two calls
+ *      and the plan cache applies.  The planes stay the caller's: mvs_sweep_set_planes(coarse, ...).
+ *   mvs_pyramid_prior(fine, coarse, coarse_depth_dev, tau)   rule U on coarse_depth_dev, (H/2)(W/2) f32 on the GPU -- NULL: the coarse
+ *      context's depth map (mvs_sweep_depth_device(coarse), after a refined sweep); mvs_sweep_band_depth_device(coarse) when the coarse
+ *      level was itself a band level -- into the fine context's own prior buffer, the one mvs_sweep_band_prior_device(fine) returns
+ *      (allocated if need be), so mvs_sweep_run_band(fine, v0, n, mvs_sweep_band_prior_device(fine), flags) runs without a copy.
+ * Ordering between the two contexts' streams is the library's job: a kernel that reads one context's buffers and writes the other's
+ * runs on the consumer's stream behind an event recorded on the producer's stream, and the producer's stream then waits for an event
+ * recorded behind that kernel, so the producer's next work cannot overwrite what is still being read.  The events are created once per
+ * context, without timing; nothing synchronises the host.  mvs_pyramid_downsample_device and mvs_pyramid_stage are timed under
+ * MVS_K_PROJECT (the stage's launches in the coarse context's profile), mvs_pyramid_prior under MVS_K_ARGMIN (in the fine context's).
+ * Errors: MVS_EINVAL for a NULL context or source, fine == coarse, contexts on different devices, W or H odd, a coarse context that is
+ * not exactly (W/2, H/2), tau outside 0..255, nframes out of range, overlapping ranges; MVS_ESTATE from mvs_pyramid_stage without a main
+ * view and side views on `fine` or with the exact sampler on either context, from mvs_pyramid_prior with a NULL coarse_depth_dev and no
+ * depth map on `coarse`, or with tau < 255 and no staged main image on either context; MVS_ENOMEM.  After an error nothing is written and
+ * both contexts stay usable (the message is on `fine`). */
+int mvs_pyramid_downsample_device(mvs_ctx *fine, const void *src_dev, void *dst_dev, int nframes);
+int mvs_pyramid_stage(mvs_ctx *fine, mvs_ctx *coarse);
+int mvs_pyramid_prior(mvs_ctx *fine, mvs_ctx *coarse, const void *coarse_depth_dev /* NULL: coarse's depth map */, int tau);
 /* The same selection in two steps, for a view-sharded job that REDUCE-SCATTERS the packed volume instead of all-reducing it
  * (half the bytes over xGMI): rank r owns the summed cells of planes [plane_first, plane_first + plane_count) in
  * `volume_slice_dev` ([plane_count][H][W] u32) and selects a partial best per pixel over them -- `partial_out_dev` receives

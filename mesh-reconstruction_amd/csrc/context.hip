@@ -276,13 +276,15 @@ void mvs_destroy(mvs_ctx *ctx)
                       &ctx->dstore_depth, &ctx->dstore_cost, &ctx->fuse_rows, &ctx->fuse_counts, &ctx->fuse_scan,
                       &ctx->tsdf_vol, &ctx->tsdf_wmaps, &ctx->tsdf_work, &ctx->tsdf_bricks, &ctx->ray_depth, &ctx->ray_normals, &ctx->agg_cost, &ctx->agg_sum,
                       &ctx->clean_labels, &ctx->clean_sizes, &ctx->clean_counters, &ctx->win_vol, &ctx->band_prior, &ctx->band_depth, &ctx->band_counters,
-                      &ctx->tsdf_app, &ctx->shade_map, &ctx->app_points, &ctx->lens_stage};
+                      &ctx->tsdf_app, &ctx->shade_map, &ctx->app_points, &ctx->lens_stage, &ctx->pyr_frames};
     for (DevBuf *b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto &lane : ctx->lanes)
         if (lane.stream) (void)hipStreamDestroy(lane.stream);
     for (hipEvent_t e : ctx->lane_events) (void)hipEventDestroy(e);
     if (ctx->plan_event) (void)hipEventDestroy(ctx->plan_event);
+    for (hipEvent_t e : ctx->pyr_events)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->band_events) (void)hipEventDestroy(e);
     for (auto &b : ctx->batch_slot) {
         if (b.swept) (void)hipEventDestroy(b.swept);
@@ -565,6 +567,8 @@ int sweep_set_views_impl(mvs_ctx *ctx, int nviews, const float *side_cams, const
         if (sync) MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->V = nviews;
+    if (nviews > 0) ctx->side_cams_host.assign(side_cams, side_cams + (size_t)nviews * 16);
+    else ctx->side_cams_host.clear();
     ctx->have_views = true;
     ctx->plan_valid = planned;
     if (planned) ctx->plan_shape = 3;

@@ -105,6 +105,7 @@ struct mvs_ctx {
     double *filter_pinned = nullptr; // mvs_filter_points: pinned host slots for the convergence value of two iterations in flight
     hipEvent_t filter_ev[2] = {nullptr, nullptr};
     std::vector<float> q_host;       // V*12
+    std::vector<float> side_cams_host;  // V*16: the side cameras the current views were staged with (mvs_pyramid_stage hands them to the coarser level)
     std::vector<float> z_host;       // D
 
     // ---- renderer state -----------------------------------------------------------------------------
@@ -208,6 +209,12 @@ struct mvs_ctx {
     mvs::DevBuf band_prior, band_depth, band_counters;
     int band_planes = 0;
     bool band_resolved = false;
+    // resolution pyramid (pyramid.hip): as the COARSE level of mvs_pyramid_stage, the (V + 1) half-resolution frames (main, then the side
+    // views) its staged state was made from, allocated by the first call; the two events that order this context's stream against the
+    // other level's ([0]: recorded when another stream is about to read this context's buffers, [1]: behind a kernel this context's
+    // stream ran on the other level's buffers), created by the first pyramid call, without timing
+    mvs::DevBuf pyr_frames;
+    hipEvent_t pyr_events[2] = {nullptr, nullptr};
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

@@ -1478,6 +1478,8 @@ int mvs_sweep_handles(mvs_ctx *ctx, int main_slot, const float main_cam[16], int
     ctx->V = 0;
     ctx->q_host.assign((size_t)nside * 12, 0.f);
     ctx->view_slots_host.assign(side_slots, side_slots + nside);
+    if (nside > 0) ctx->side_cams_host.assign(side_cams, side_cams + (size_t)nside * 16);
+    else ctx->side_cams_host.clear();
     if (nside > 0) {
         if ((rc = ensure(ctx, ctx->qmats, sizeof(float) * 12 * nside))) return rc;
         if ((rc = ensure(ctx, ctx->view_slots, sizeof(int) * 256))) return rc;

@@ -135,6 +135,9 @@ ABI = [
     ("mvs_sweep_band_prior_device", _vp, [_vp]),
     ("mvs_sweep_band_fetch", _i, [_vp, _fp]),
     ("mvs_sweep_band_report", _i, [_vp, C.POINTER(_i)]),
+    ("mvs_pyramid_downsample_device", _i, [_vp, _vp, _vp, _i]),
+    ("mvs_pyramid_stage", _i, [_vp, _vp]),
+    ("mvs_pyramid_prior", _i, [_vp, _vp, _vp, _i]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
     ("mvs_sweep_combine_partials", _i, [_vp, _vp, _i]),
     ("mvs_sweep_volume_device", _vp, [_vp, C.POINTER(_sz)]),
@@ -432,6 +435,35 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     ctx.sweep_run_band(ctx.sweep_result_pointers()[0], 0, None, flags)
     ctx.sweep_refine_depth()
     return ctx.sweep_band_resolve(fetch=fetch)
+
+
+def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, tau=255, fetch=True):
+    """Coarse-to-fine over a resolution pyramid: ctxs = [fine, half] or [fine, half, quarter], each level a context
+    of exactly half the size of the one before it, on one GPU, with the inputs staged on ctxs[0].  Stages down the chain (pyramid_stage);
+    coarsest level: `coarse_planes` planes over [z_lo, z_hi], refined; each finer level: its prior from the level below (pyramid_prior with
+    `tau`), then `band_planes` planes within +- band_steps plane steps of the level below (a band level's step is its band width over
+    band_planes), refined and resolved.  Pure composition of Context calls, like coarse_to_fine -> the finest level's absolute depth map
+    (H, W) float32 (fetch=False: None, the map stays on the device: ctxs[0].sweep_band_pointers()[0]); every level is left with its own
+    plane table, volume and maps."""
+    flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
+    for above, below in zip(ctxs, ctxs[1:]):
+        above.pyramid_stage(below)
+    ctxs[-1].sweep_set_planes(coarse_planes, z_lo, z_hi)
+    ctxs[-1].sweep_run(0, None, flags)
+    ctxs[-1].sweep_refine_depth()
+    step = (float(z_hi) - float(z_lo)) / coarse_planes
+    depth_ptr, out = None, None            # None: the depth map of the level below
+    for level in range(len(ctxs) - 2, -1, -1):
+        ctx = ctxs[level]
+        ctx.pyramid_prior(ctxs[level + 1], depth_ptr, tau)
+        hb = float(np.float32(band_steps * step))
+        ctx.sweep_set_planes(band_planes, -hb, hb)
+        ctx.sweep_run_band(ctx.sweep_band_pointers()[1], 0, None, flags)
+        ctx.sweep_refine_depth()
+        out = ctx.sweep_band_resolve(fetch=fetch and level == 0)
+        depth_ptr = ctx.sweep_band_pointers()[0]
+        step = 2.0 * hb / band_planes
+    return out
 
 
 class Comm:
@@ -1129,6 +1161,26 @@ class Context:
     def sweep_band_pointers(self):
         """(device address of band_depth, of the context's copy of the prior); 0 before the first resolve / band run"""
         return self.lib.mvs_sweep_band_depth_device(self.h) or 0, self.lib.mvs_sweep_band_prior_device(self.h) or 0
+
+    # ---- resolution pyramid (include/mvs.h, DESIGN.md section 20) --------------------------------
+    def pyramid_downsample_device(self, src_ptr, dst_ptr, nframes=1):
+        """mvs_pyramid_downsample_device: nframes tightly packed H*W u8 frames -> (H/2)*(W/2) frames (rounded 2 x 2 means), device
+        addresses, one launch (stream-ordered)"""
+        self._check(self.lib.mvs_pyramid_downsample_device(self.h, C.c_void_p(int(src_ptr)), C.c_void_p(int(dst_ptr)), int(nframes)))
+
+    def pyramid_stage(self, coarse):
+        """mvs_pyramid_stage: stages on `coarse` (a Context of exactly half this one's size) the half-resolution copy of what is staged
+        here: main image, side views, the same cameras.  The planes stay the caller's: coarse.sweep_set_planes"""
+        self._check(self.lib.mvs_pyramid_stage(self.h, coarse.h))
+        if hasattr(self, "V"):
+            coarse.V = self.V
+
+    def pyramid_prior(self, coarse, depth_ptr=None, tau=255):
+        """mvs_pyramid_prior: the coarse level's depth map (depth_ptr: device address of (H/2)*(W/2) f32; None: coarse's own depth map)
+        upsampled into this context's prior buffer, sweep_band_pointers()[1], which is returned; tau < 255 keeps to the taps whose guide
+        pixel is within tau grey levels of this pixel's (the staged main images are the guides)"""
+        self._check(self.lib.mvs_pyramid_prior(self.h, coarse.h, C.c_void_p(int(depth_ptr)) if depth_ptr else None, int(tau)))
+        return self.lib.mvs_sweep_band_prior_device(self.h)
 
     def sweep_argmin_partial(self, volume_slice_ptr, plane_first, plane_count, partial_out_ptr):
         self._check(self.lib.mvs_sweep_argmin_partial(self.h, C.c_void_p(volume_slice_ptr), int(plane_first), int(plane_count),
