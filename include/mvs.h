@@ -124,6 +124,12 @@ int mvs_texture_filter(const mvs_ctx *ctx);
  * distances as the reference does).  keep_out receives the ascending indices of the retained points, *out_count how
  * many; the caller compacts points and normals with them (heuristic.cpp:166-175). */
 int mvs_filter_points(mvs_ctx *ctx, const float *points4, int npoints, float alpha, int32_t *keep_out, int *out_count);
+/* The npoints densities (heuristic.cpp:103-136, after the last counted update) the last successful mvs_filter_points of this context
+ * ranked its points by, in input order; they stay on the device in a buffer no other stage writes, so calls of other stages in between
+ * do not disturb them.  MVS_ESTATE before any mvs_filter_points, after one that failed and after one with npoints = 0.  Synchronises.
+ * mvs_filter_density_count: how many densities the fetch would write (0 where it would return MVS_ESTATE, and for a NULL ctx). */
+int mvs_filter_density_fetch(mvs_ctx *ctx, float *density_n);
+int mvs_filter_density_count(const mvs_ctx *ctx);
 
 /* ---- plane sweep: the D-plane generalisation of shader.frag:11-25 ------ */
 /*

@@ -4,7 +4,8 @@
 // Reference structure -> here (everything on the device; the host only reads an 8-byte convergence value per power
 // iteration, a round counter per batch of greedy rounds, and the final keep flags):
 //   FLANN KD-tree build + one radiusSearch per point (heuristic.cpp:74-92, single thread, randomised, approximate)
-//       -> hash grid with cell = sqrt(radius): hash_build, nb_count, nb_fill (exact neighbourhood, 27 cells per point);
+//       -> hash grid with cell = sqrt(radius) padded by 2^-18, indices in f64: hash_build, nb_count, nb_fill (exact neighbourhood,
+//          27 cells per point, beyond the +-1e9 clamp of the index too: the bound is at grid_cell below);
 //          every point gets its lower list (j < i) and its upper list (k > i), both ascending by index so the result does
 //          not depend on atomics' arrival order -- ordered per thread for short lists, by global radix sorts with key
 //          (owner, index) for long ones (list_keys)
@@ -38,7 +39,23 @@ __device__ __forceinline__ unsigned cell_hash(int cx, int cy, int cz, unsigned m
     return ((unsigned)cx * 73856093u ^ (unsigned)cy * 19349663u ^ (unsigned)cz * 83492791u) & mask;
 }
 
-__global__ __launch_bounds__(256) void dehomog_cells(const float *__restrict__ p4, int N, float inv_cell, float *__restrict__ p3,
+// The side of a grid cell for `radius`, such that every pair the reference accepts (float d2 <= radius) is at most one cell apart on
+// every axis.  With u = 2^-24 and c = sqrt(radius):
+//   d2 <= radius  =>  fl(dx * dx) <= radius (the other two terms are >= 0 and rounding is monotone)  =>  dx * dx <= radius (1 + u)
+//                 =>  |dx| <= c (1 + u / 2), and dx = fl(x_i - x_j), so the real difference is |x_i - x_j| <= c (1 + u / 2) / (1 - u) < c (1 + 2^-23)
+//   (a subnormal radius, or a dx * dx that underflows: dx * dx <= radius + 2^-150 instead, which the 2^-150 under the root covers; it
+//   vanishes in f64 next to any normal radius)
+//   the cell is c (1 + 2^-18) in f64 (sqrt and product: 2 roundings of 2^-53), so the real quotients q = x / cell of such a pair
+//   differ by less than (1 + 2^-23) / (1 + 2^-18 - 2^-51) < 1 - 2^-18 + 2^-22
+//   the index is floor(fl64(x * fl64(1 / cell))): 2 roundings, |q' - q| <= 2^-51.9 |q|, so while |q| < 2^30 the computed quotients
+//   differ by less than 1 - 2^-18 + 2^-22 + 2 * 2^-21.9 < 1 and the floors by at most 1
+//   the clamp to +-1e9 < 2^30 - 2 is monotone and moves no two integers further apart: a pair that straddles it stays within one cell,
+//   and a pair wholly beyond 2^30 - 2 is clamped into one cell (its quotients are one apart at most, so they have the same sign).
+// (In f32 -- sqrtf, 1.0f / cell, floorf(v * inv) -- the product alone is off by up to 2^-24 |q|: half a cell at index 2^23, and a pair on
+// either side of 0 at distance exactly fl(c) landed in cells -1 and +1.)
+static double grid_cell(float radius) { return std::sqrt((double)radius + 0x1p-150) * (1. + 0x1p-18); }
+
+__global__ __launch_bounds__(256) void dehomog_cells(const float *__restrict__ p4, int N, double inv_cell, float *__restrict__ p3,
                                                      int *__restrict__ cell3)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -47,8 +64,8 @@ __global__ __launch_bounds__(256) void dehomog_cells(const float *__restrict__ p
     for (int c = 0; c < 3; c++) {
         const float v = p4[4 * i + c] / p4[4 * i + 3];  // dehomogenize, util.cpp:16-29
         p3[3 * i + c] = v;
-        const float f = floorf(v * inv_cell);
-        cell3[3 * i + c] = (int)fminf(fmaxf(f, -1.0e9f), 1.0e9f);
+        const double f = floor((double)v * inv_cell);
+        cell3[3 * i + c] = (int)fmin(fmax(f, -1.0e9), 1.0e9);  // NaN -> -1e9
     }
 }
 
@@ -334,6 +351,7 @@ extern "C" {
 
 int mvs_filter_points(mvs_ctx *ctx, const float *points4, int npoints, float alpha, int32_t *keep_out, int *out_count)
 {
+    if (ctx) ctx->filter_density_n = 0;  // mvs_filter_density_fetch: nothing to fetch until this call has succeeded
     if (!ctx || !out_count || npoints < 0 || (npoints > 0 && (!points4 || !keep_out)))
         return fail(ctx, MVS_EINVAL, "mvs_filter_points: bad arguments");
     *out_count = 0;
@@ -357,14 +375,16 @@ int mvs_filter_points(mvs_ctx *ctx, const float *points4, int npoints, float alp
     unsigned table = 1;
     while (table < 2u * (unsigned)N) table <<= 1;
     const unsigned mask = table - 1;
-    const float cell = std::sqrt(radius);
+    const double cell = grid_cell(radius);
 
     // pass 1 buffers
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_p4 = al(sizeof(float) * 4 * N), b_p3 = al(sizeof(float) * 3 * N), b_c3 = al(sizeof(int) * 3 * N), b_head = al(sizeof(int) * table),
                  b_n1 = al(sizeof(int) * ((size_t)N + 1));
-    int rc = ensure(ctx, ctx->flow_arena, b_p4 + b_p3 + b_c3 + b_head + 6 * b_n1 + 4 * al(sizeof(float) * N) + 2 * al(sizeof(double) * N) + 8192);
+    int rc = ensure(ctx, ctx->flow_arena, b_p4 + b_p3 + b_c3 + b_head + 6 * b_n1 + 2 * al(sizeof(float) * N) + 2 * al(sizeof(double) * N) + 8192);
     if (rc) return rc;
+    // the two densities of the ping-pong live in a buffer no other stage uses: mvs_filter_density_fetch reads the final one later
+    if ((rc = ensure(ctx, ctx->filter_density, 2 * al(sizeof(float) * N)))) return rc;
     char *base = (char *)ctx->flow_arena.ptr;
     float *d_p4 = (float *)base;
     float *d_p3 = (float *)(base += b_p4);
@@ -373,8 +393,8 @@ int mvs_filter_points(mvs_ctx *ctx, const float *points4, int npoints, float alp
     int *d_next = (int *)(base += b_head);
     int *d_cnt_lo = (int *)(base += b_n1), *d_cnt_up = (int *)(base += b_n1), *d_off_lo = (int *)(base += b_n1), *d_off_up = (int *)(base += b_n1),
         *d_fill = (int *)(base += b_n1);
-    float *d_density = (float *)(base += b_n1), *d_score = (float *)(base += al(sizeof(float) * N));
-    float *d_density_b = (float *)(base += al(sizeof(float) * N)), *d_score_b = (float *)(base += al(sizeof(float) * N));
+    float *d_score = (float *)(base += b_n1), *d_score_b = (float *)(base += al(sizeof(float) * N));
+    float *d_density = (float *)ctx->filter_density.ptr, *d_density_b = (float *)((char *)ctx->filter_density.ptr + al(sizeof(float) * N));
     double *d_pair = (double *)(base += al(sizeof(float) * N)), *d_chg = (double *)(base += al(sizeof(double) * N));
     double *d_256 = (double *)(base += al(sizeof(double) * N));
 
@@ -384,7 +404,7 @@ int mvs_filter_points(mvs_ctx *ctx, const float *points4, int npoints, float alp
     MVS_HIP(ctx, hipMemsetAsync(d_cnt_lo, 0, sizeof(int) * ((size_t)N + 1), st));
     MVS_HIP(ctx, hipMemsetAsync(d_fill, 0, sizeof(int) * ((size_t)N + 1), st));
     const unsigned g = (unsigned)div_up(N, 256);
-    dehomog_cells<<<g, 256, 0, st>>>(d_p4, N, 1.0f / cell, d_p3, d_c3);
+    dehomog_cells<<<g, 256, 0, st>>>(d_p4, N, 1. / cell, d_p3, d_c3);
     hash_build<<<g, 256, 0, st>>>(d_c3, N, mask, d_head, d_next);
     nb_count<<<g, 256, 0, st>>>(d_p3, d_c3, d_head, d_next, mask, N, radius, d_cnt_lo, d_cnt_up);
     {
@@ -568,8 +588,24 @@ int mvs_filter_points(mvs_ctx *ctx, const float *points4, int npoints, float alp
     for (int i = 0; i < N; i++)
         if (state[i] == 1) keep_out[m++] = i;
     *out_count = m;
+    ctx->filter_density_n = N;
+    ctx->filter_density_off = (size_t)((char *)d_density - (char *)ctx->filter_density.ptr);
     lap("device greedy rounds + output");
     return MVS_OK;
 }
+
+int mvs_filter_density_fetch(mvs_ctx *ctx, float *density_n)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_filter_density_fetch: null context");
+    if (!density_n) return fail(ctx, MVS_EINVAL, "mvs_filter_density_fetch: density_n is null");
+    if (ctx->filter_density_n <= 0) return fail(ctx, MVS_ESTATE, "mvs_filter_density_fetch: no successful mvs_filter_points with npoints > 0 on this context yet");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    MVS_HIP(ctx, hipMemcpyAsync(density_n, (const char *)ctx->filter_density.ptr + ctx->filter_density_off, sizeof(float) * (size_t)ctx->filter_density_n,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MVS_OK;
+}
+
+int mvs_filter_density_count(const mvs_ctx *ctx) { return ctx ? ctx->filter_density_n : 0; }
 
 }  // extern "C"

@@ -104,6 +104,9 @@ struct mvs_ctx {
     mvs::DevBuf filter_sort;         // mvs_filter_points, dense clouds: keys and a second copy of the upper lists for the global sorts
     double *filter_pinned = nullptr; // mvs_filter_points: pinned host slots for the convergence value of two iterations in flight
     hipEvent_t filter_ev[2] = {nullptr, nullptr};
+    mvs::DevBuf filter_density;      // mvs_filter_points: the two density buffers of the power iteration (no other stage touches them);
+    int filter_density_n = 0;        // mvs_filter_density_fetch: N of the last successful call (0: nothing to fetch) and the byte offset of
+    size_t filter_density_off = 0;   // the buffer its greedy pass ranked by
     std::vector<float> q_host;       // V*12
     std::vector<float> side_cams_host;  // V*16: the side cameras the current views were staged with (mvs_pyramid_stage hands them to the coarser level)
     std::vector<float> z_host;       // D

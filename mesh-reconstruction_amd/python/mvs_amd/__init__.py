@@ -59,6 +59,8 @@ ABI = [
     ("mvs_process_frame", _i, [_vp, _fp, _u8p, _i, _fp, C.POINTER(_u8p), _i, _fp, C.POINTER(_i), _fp]),
     ("mvs_process_frame_slots", _i, [_vp, _fp, _i, _i, _fp, _i32p, _i, _fp, C.POINTER(_i), _fp]),
     ("mvs_filter_points", _i, [_vp, _fp, _i, _f, _i32p, C.POINTER(_i)]),
+    ("mvs_filter_density_fetch", _i, [_vp, _fp]),
+    ("mvs_filter_density_count", _i, [_vp]),
     ("mvs_sweep", _i, [_vp, _fp, _u8p, _i, _fp, C.POINTER(_u8p), _i, _f, _f, _fp, _fp, _fp]),
     ("mvs_warp_by_depth", _i, [_vp, _fp, _fp, _fp, _u8p, _u8p]),
     ("mvs_sweep_set_sampler", _i, [_vp, _i]),
@@ -1369,6 +1371,13 @@ class Context:
         n = C.c_int(0)
         self._check(self.lib.mvs_filter_points(self.h, _ptr(pts, _fp), pts.shape[0], float(alpha), _ptr(keep, _i32p), C.byref(n)))
         return keep[:n.value].copy()
+
+    def filter_density(self):
+        """mvs_filter_density_fetch -> (N,) float32 densities the last successful filter_points ranked its points by (synchronises)"""
+        n = self.lib.mvs_filter_density_count(self.h)   # the library's own N; 0: the fetch reports why there is nothing
+        dens = np.empty(max(n, 1), np.float32)
+        self._check(self.lib.mvs_filter_density_fetch(self.h, _ptr(dens, _fp)))
+        return dens[:n]
 
     def onecall_bands(self):
         """test hook: the row bands the last one-call sweep() of this context was pipelined in (0: the unbanded path)"""
