@@ -350,6 +350,38 @@ void *mvs_sweep_band_depth_device(mvs_ctx *ctx);
 void *mvs_sweep_band_prior_device(mvs_ctx *ctx);
 int mvs_sweep_band_fetch(mvs_ctx *ctx, float *depth_hw);
 int mvs_sweep_band_report(mvs_ctx *ctx, int out[4]);
+/* ZNCC sweep: zero-mean normalised cross-correlation over a support window as the matching cost (csrc/zncc.hip; DESIGN.md section 21 is
+ * the arithmetic contract; the window sums are exact integers, the last steps f32 with one rounding per operation and no contraction;
+ * bit-identical to tests/zncc_mirror.py).  Fixed sampler only.  The cost of mvs_sweep_run, |dot - 255 I_main|, assumes that a surface
+ * point has the same grey level in every frame; this one is invariant to a local affine change of intensity (exposure, vignetting).
+ * The planes are the context's plane table z_d, the views [view_first, view_first + view_count), radius 1..4.
+ *   1. Warped grey level: for pixel q, plane d, view v the fixed sampler's sample at (xn(q), yn(q), z_d) -- the sample of mvs_sweep_run,
+ *      bit for bit -- has a frame test ok(q) and a weighted sum dot; B(q) = (dot + 127) / 255 in integer division, the grey level
+ *      mvs_warp_by_depth returns with the fixed sampler.  A(q) is the staged main image.
+ *   2. Members: for the centre pixel p the window M is every pixel q of the frame with |q.row - p.row| <= radius,
+ *      |q.col - p.col| <= radius and ok(q); pixels outside the frame are no members.  The view counts for the cell only if ok(p).
+ *   3. Sums over M: N = |M|, Sa, Sb, Sab, Saa, Sbb of A, B, A B, A A, B B; cov = N Sab - Sa Sb, va = N Saa - Sa Sa, vb = N Sbb - Sb Sb
+ *      (all below 2^31 at radius 4).  The view counts only if va > 0 and vb > 0: a flat patch carries no correlation and is treated
+ *      like a sample out of frame.
+ *   4. Cost of a counted view: den = sqrtf((float)va * (float)vb); ncc = (float)cov / den, clamped to [-1, 1];
+ *      c = (uint32)floorf(32512.0f * (1.0f - ncc)), 0..65024.
+ *   5. Cell: the sum of (1 << 24) + c over the counted views of the listed range, 0 if there are none; layout [D][H][W] u32 in the
+ *      context's packed volume (its own or the caller's).  As in mvs_sweep_run the cells are the sums of the listed views, not added to
+ *      what was there; the volumes of disjoint view ranges add as u32, so the view-sharded reductions stay valid.
+ *   6. Reading the cost map: every reader takes a cell's mean cost as sum / (255 count), so the cost map reads 127.5 (1 - ncc) "grey
+ *      levels": 0 is perfect correlation, 127.5 none, 255 inverted.  That is the scale of mvs_fuse_depth's max_cost, of
+ *      mvs_sweep_aggregate's cost_cap (in 1/16 of it) and of what mvs_sweep_clean's uniqueness_percent compares on this volume.
+ *   7. Selection: MVS_SWEEP_FUSED_ARGMIN gives what mvs_sweep_argmin gives on that volume (lowest mean as an exact rational, ties to the
+ *      lowest plane, -1 / MVS_BACKGROUND_DEPTH / +inf where nothing is counted) and records a full selection over the current plane
+ *      count; without the flag the context has no depth selection until a selecting call, as after a band run.
+ * For every later call it is an ordinary sweep (mvs_sweep_argmin, _refine_depth, _window, _aggregate, _clean, the depth store and the TSDF
+ * run on its result unchanged; it ends a band run's state exactly as mvs_sweep_run does).  It works on the staged state however it got
+ * there (host setters, the _device forms, the slots left staged by mvs_sweep_handles), is asynchronous on the context's stream and timed
+ * under MVS_K_SWEEP.  A context that never calls it allocates nothing for it.
+ * Errors: MVS_EINVAL for a NULL ctx, radius outside 1..4, a view range outside 0..V, flags that select neither output, unknown flag bits
+ * (MVS_SWEEP_FORCE_GENERIC and MVS_SWEEP_NO_RECT are unknown here), a caller's volume that is too small; MVS_ESTATE without main view,
+ * views or planes, for the exact sampler; MVS_ENOMEM.  After an error nothing is written and the context stays usable. */
+int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius, unsigned flags);
 /* Resolution pyramid: a half-resolution coarse level for the band sweep (csrc/pyramid.hip; DESIGN.md section 20 is the contract;
  * bit-identical to tests/pyramid_mirror.py).  The levels are separate contexts on the SAME GPU: `fine` is W x H with W and H even,
  * `coarse` exactly (W/2) x (H/2).  The cameras are NDC matrices and the centre of a coarse pixel is the mean of the centres of its four

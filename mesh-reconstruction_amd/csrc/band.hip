@@ -131,24 +131,6 @@ __global__ __launch_bounds__(256) void band_resolve(const float *__restrict__ pr
     }
 }
 
-// the maps and, for a volume run, the packed volume of the current planes (what sweep.hip's ensure_outputs gives mvs_sweep_run)
-int band_outputs(mvs_ctx *ctx, bool need_volume)
-{
-    const size_t P = (size_t)ctx->W * ctx->H;
-    int rc;
-    if (need_volume && ctx->volume_external && ctx->volume_bytes < P * (size_t)ctx->D * sizeof(uint32_t))
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: caller volume is %zu bytes, need %zu", ctx->volume_bytes, P * (size_t)ctx->D * sizeof(uint32_t));
-    if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->cost, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->index, P * sizeof(int)))) return rc;
-    if (need_volume && !ctx->volume_external) {
-        if ((rc = ensure(ctx, ctx->volume_own, P * (size_t)ctx->D * sizeof(uint32_t)))) return rc;
-        ctx->volume = (uint32_t *)ctx->volume_own.ptr;
-        ctx->volume_bytes = ctx->volume_own.bytes;
-    }
-    return MVS_OK;
-}
-
 // resolve, fetch and report work on the maps of a band run: one happened, no ordinary sweep since, and the index map is a selection over
 // the planes the band run had
 int band_state(mvs_ctx *ctx, const char *who)
@@ -188,7 +170,7 @@ int mvs_sweep_run_band(mvs_ctx *ctx, int view_first, int view_count, const void 
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)ctx->W * ctx->H;
     int rc;
-    if ((rc = band_outputs(ctx, vol))) return rc;
+    if ((rc = sweep_outputs(ctx, vol, "mvs_sweep_run_band"))) return rc;
     if ((rc = ensure(ctx, ctx->band_prior, P * sizeof(float)))) return rc;
     if ((rc = ensure_fx_lut(ctx))) return rc;
     // the context's own copy: the caller's map may be the depth map this run overwrites (stream order puts the copy first)

@@ -231,6 +231,25 @@ inline int fill_params(mvs_ctx *ctx, SweepParams &p, int v0, int vcount, int til
     return MVS_OK;
 }
 
+// host: the maps and, for a volume run, the packed volume of the current planes (what sweep.hip's ensure_outputs gives mvs_sweep_run), for the
+// sweep entry points outside sweep.hip; a caller's volume that is too small is refused before anything is allocated
+inline int sweep_outputs(mvs_ctx *ctx, bool need_volume, const char *who)
+{
+    const size_t P = (size_t)ctx->W * ctx->H, need = P * (size_t)ctx->D * sizeof(uint32_t);
+    int rc;
+    if (need_volume && ctx->volume_external && ctx->volume_bytes < need)
+        return fail(ctx, MVS_EINVAL, "%s: caller volume is %zu bytes, need %zu", who, ctx->volume_bytes, need);
+    if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
+    if ((rc = ensure(ctx, ctx->cost, P * sizeof(float)))) return rc;
+    if ((rc = ensure(ctx, ctx->index, P * sizeof(int)))) return rc;
+    if (need_volume && !ctx->volume_external) {
+        if ((rc = ensure(ctx, ctx->volume_own, need))) return rc;
+        ctx->volume = (uint32_t *)ctx->volume_own.ptr;
+        ctx->volume_bytes = ctx->volume_own.bytes;
+    }
+    return MVS_OK;
+}
+
 // host: narrows filled parameters to planes [plane_first, +plane_count) and rows [row_first, +row_count), in the units of the shape
 // they were filled for (p.pc planes per chunk, tiles of p.tile_h rows) and in planes / pixels
 inline void narrow_params(SweepParams &p, int plane_first, int plane_count, int row_first, int row_count)

@@ -137,6 +137,7 @@ ABI = [
     ("mvs_sweep_band_prior_device", _vp, [_vp]),
     ("mvs_sweep_band_fetch", _i, [_vp, _fp]),
     ("mvs_sweep_band_report", _i, [_vp, C.POINTER(_i)]),
+    ("mvs_sweep_run_zncc", _i, [_vp, _i, _i, _i, C.c_uint]),
     ("mvs_pyramid_downsample_device", _i, [_vp, _vp, _vp, _i]),
     ("mvs_pyramid_stage", _i, [_vp, _vp]),
     ("mvs_pyramid_prior", _i, [_vp, _vp, _vp, _i]),
@@ -1163,6 +1164,14 @@ class Context:
     def sweep_band_pointers(self):
         """(device address of band_depth, of the context's copy of the prior); 0 before the first resolve / band run"""
         return self.lib.mvs_sweep_band_depth_device(self.h) or 0, self.lib.mvs_sweep_band_prior_device(self.h) or 0
+
+    def sweep_run_zncc(self, radius=2, view_first=0, view_count=None, flags=MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN):
+        """mvs_sweep_run_zncc: the fixed sampler's sweep with zero-mean normalised cross-correlation over the (2 radius + 1)^2 window as
+        the matching cost (radius 1..4); the same packed volume and maps as sweep_run, the cost map reads 127.5 (1 - ncc)
+        (asynchronous, stream-ordered)"""
+        if view_count is None:
+            view_count = self.V - view_first
+        self._check(self.lib.mvs_sweep_run_zncc(self.h, int(view_first), int(view_count), int(radius), int(flags)))
 
     # ---- resolution pyramid (include/mvs.h, DESIGN.md section 20) --------------------------------
     def pyramid_downsample_device(self, src_ptr, dst_ptr, nframes=1):

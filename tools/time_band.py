@@ -40,8 +40,8 @@ def spread(values):
     return {"median": round(v[len(v) // 2], 5), "min": round(v[0], 5), "max": round(v[-1], 5)}
 
 
-def kernel_ms(ctx, call, iters):
-    """HIP-event time of the MVS_K_SWEEP launches of one call, per iteration"""
+def kernel_ms(ctx, call, iters, kinds=(mvs_amd.MVS_K_SWEEP,)):
+    """HIP-event time of the launches of one call that the library times under `kinds`, per iteration"""
     for _ in range(3):
         call()
     ctx.synchronize()
@@ -51,7 +51,7 @@ def kernel_ms(ctx, call, iters):
     for _ in range(iters):
         call()
         ms, _ = ctx.profile_read(reset=True)
-        out.append(float(ms[mvs_amd.MVS_K_SWEEP]))
+        out.append(float(sum(ms[k] for k in kinds)))
     ctx.profile_enable(False)
     return out
 
@@ -59,18 +59,7 @@ def kernel_ms(ctx, call, iters):
 def launch_ms(ctx, call, iters):
     """HIP-event time of every timed launch of one call (sweep, selection and resolve, planning; mvs_sweep_refine_depth is not timed by
     the library), per iteration"""
-    for _ in range(3):
-        call()
-    ctx.synchronize()
-    ctx.profile_enable(True)
-    ctx.profile_read(reset=True)
-    out = []
-    for _ in range(iters):
-        call()
-        ms, _ = ctx.profile_read(reset=True)
-        out.append(float(ms[mvs_amd.MVS_K_SWEEP] + ms[mvs_amd.MVS_K_ARGMIN] + ms[mvs_amd.MVS_K_PLAN]))
-    ctx.profile_enable(False)
-    return out
+    return kernel_ms(ctx, call, iters, (mvs_amd.MVS_K_SWEEP, mvs_amd.MVS_K_ARGMIN, mvs_amd.MVS_K_PLAN))
 
 
 def wall_ms(ctx, call, iters):
