@@ -15,7 +15,7 @@
 //                        waves exchange their partial minimum and their boundary planes through LDS with one barrier per row.  The next
 //                        row's C and S are loaded before the current row is computed.  S += L; the launch owns every cell it touches.
 //   agg_select_kernel    a pixel per lane, planes streamed: lowest plane with the smallest S among the seen cells, cost, depth and
-//                        (MVS_AGGREGATE_REFINE) the parabola of refine_depth (sweep.hip) on (float)S.
+//                        (MVS_AGGREGATE_REFINE) the parabola of select_rules.hpp on (float)S.
 // No atomics, no scalar memory writes; results do not depend on the launch order (integer sums commute).
 #include "sweep_shared.hpp"
 
@@ -299,16 +299,8 @@ __global__ __launch_bounds__(256) void agg_select_kernel(const uint16_t *__restr
     float zr = z[bi];
     if (refine && bi > 0 && bi < D - 1) {
         const size_t a = (size_t)(bi - 1) * P + p, c = (size_t)(bi + 1) * P + p;
-        if ((vol[a] >> CS) != 0u && (vol[c] >> CS) != 0u) {
-            // refine_depth (sweep.hip) with (float)S in place of the mean costs: same operations, same order
-            const float ca = (float)S[a], cb = (float)best, cc = (float)S[c];
-            const float den = (ca - 2.0f * cb) + cc;
-            if (den > 0.0f) {
-                float t = (0.5f * (ca - cc)) / den;
-                t = t < -0.5f ? -0.5f : (t > 0.5f ? 0.5f : t);
-                zr = t >= 0.0f ? __builtin_fmaf(t, z[bi + 1] - z[bi], z[bi]) : __builtin_fmaf(-t, z[bi - 1] - z[bi], z[bi]);
-            }
-        }
+        // the volume's counts say which neighbours are seen; the parabola runs on (float)S in place of the mean costs
+        if ((vol[a] >> CS) != 0u && (vol[c] >> CS) != 0u) zr = refine_parabola((float)S[a], (float)best, (float)S[c], z, bi, D);
     }
     depth[p] = zr;
 }
@@ -343,24 +335,18 @@ int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, u
     const int W = ctx->W, H = ctx->H, D = ctx->D;
     if (D < 2 || D > kAggMaxPlanes) return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: %d planes outside 2..%d", D, kAggMaxPlanes);
     const size_t P = (size_t)W * H, N = P * (size_t)D;
-    if (vol_bytes < N * sizeof(uint32_t))
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: the volume is %zu bytes, %d planes need %zu", vol_bytes, D, N * sizeof(uint32_t));
+    if (vol_bytes < volume_need(ctx))
+        return fail(ctx, MVS_EINVAL, "mvs_sweep_aggregate: the volume is %zu bytes, %d planes need %zu", vol_bytes, D, volume_need(ctx));
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
-    if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->cost, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->index, P * sizeof(int)))) return rc;
+    if ((rc = ensure_maps(ctx))) return rc;
     ctx->agg_planes = 0;   // no S until every launch of this call is queued
     if ((rc = ensure(ctx, ctx->agg_sum, N * sizeof(uint16_t)))) return rc;
     if ((rc = ensure(ctx, ctx->agg_cost, N * sizeof(uint16_t)))) return rc;
     uint16_t *C = (uint16_t *)ctx->agg_cost.ptr, *S = (uint16_t *)ctx->agg_sum.ptr;
-    const bool fx = ctx->sampler == MVS_SAMPLER_FIXED;
     ProfileScope ps(ctx, MVS_K_ARGMIN);
     const unsigned cblocks = (unsigned)((N + 255) / 256);
-    if (fx)
-        agg_cost_kernel<CS_FIXED><<<cblocks, 256, 0, ctx->stream>>>(vol, N, (uint32_t)cost_cap, C);
-    else
-        agg_cost_kernel<CS_EXACT><<<cblocks, 256, 0, ctx->stream>>>(vol, N, (uint32_t)cost_cap, C);
+    with_cells(ctx, [&](auto cs) { agg_cost_kernel<decltype(cs)::value><<<cblocks, 256, 0, ctx->stream>>>(vol, N, (uint32_t)cost_cap, C); });
     MVS_HIP(ctx, hipGetLastError());
     // paths (0, +1) and (0, -1): the launch that stores S
     if (D <= 64)
@@ -383,12 +369,10 @@ int mvs_sweep_aggregate(mvs_ctx *ctx, int paths, int p1, int p2, int cost_cap, u
     const float cost_div = (float)(16 * paths);
     const int refine = (flags & MVS_AGGREGATE_REFINE) ? 1 : 0;
     const unsigned sblocks = (unsigned)((P + 255) / 256);
-    if (fx)
-        agg_select_kernel<CS_FIXED><<<sblocks, 256, 0, ctx->stream>>>(S, vol, P, D, (const float *)ctx->ztab.ptr, cost_div, refine, (float *)ctx->depth.ptr,
-                                                                      (float *)ctx->cost.ptr, (int *)ctx->index.ptr);
-    else
-        agg_select_kernel<CS_EXACT><<<sblocks, 256, 0, ctx->stream>>>(S, vol, P, D, (const float *)ctx->ztab.ptr, cost_div, refine, (float *)ctx->depth.ptr,
-                                                                      (float *)ctx->cost.ptr, (int *)ctx->index.ptr);
+    with_cells(ctx, [&](auto cs) {
+        agg_select_kernel<decltype(cs)::value><<<sblocks, 256, 0, ctx->stream>>>(S, vol, P, D, (const float *)ctx->ztab.ptr, cost_div, refine, (float *)ctx->depth.ptr,
+                                                                                 (float *)ctx->cost.ptr, (int *)ctx->index.ptr);
+    });
     MVS_HIP(ctx, hipGetLastError());
     ctx->agg_planes = D;
     note_full_selection(ctx);

@@ -138,7 +138,7 @@ int band_state(mvs_ctx *ctx, const char *who)
     if (!ctx->band_planes) return fail(ctx, MVS_ESTATE, "%s: no band run yet, or an ordinary sweep since (mvs_sweep_run_band first)", who);
     if (!ctx->have_planes || ctx->D != ctx->band_planes)
         return fail(ctx, MVS_ESTATE, "%s: the band run had %d planes, the context now has %d (run the band again)", who, ctx->band_planes, ctx->D);
-    if (ctx->sel_planes != ctx->D || !ctx->index.ptr)
+    if (!selection_current(ctx) || !ctx->index.ptr)
         return fail(ctx, MVS_ESTATE, "%s: no depth selection over the current %d planes (MVS_SWEEP_FUSED_ARGMIN, or mvs_sweep_argmin)", who, ctx->D);
     return MVS_OK;
 }
@@ -153,23 +153,14 @@ int mvs_sweep_run_band(mvs_ctx *ctx, int view_first, int view_count, const void 
 {
     if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_sweep_run_band: null context");
     if (!prior_dev) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: prior_dev is null");
-    if (flags & ~(MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN))
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: unknown flag bits 0x%x (MVS_SWEEP_VOLUME and MVS_SWEEP_FUSED_ARGMIN only)",
-                    flags & ~(MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN));
-    const bool vol = (flags & MVS_SWEEP_VOLUME) != 0, fused = (flags & MVS_SWEEP_FUSED_ARGMIN) != 0;
-    if (!vol && !fused) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: flags select neither volume nor fused argmin");
-    if (!ctx->have_main || !ctx->have_views || !ctx->have_planes) return fail(ctx, MVS_ESTATE, "mvs_sweep_run_band: set main view, side views and planes first");
-    if (ctx->sampler != MVS_SAMPLER_FIXED) return fail(ctx, MVS_ESTATE, "mvs_sweep_run_band: implemented for MVS_SAMPLER_FIXED (the library default)");
+    bool vol, fused;
+    int rc;
+    if ((rc = fx_sweep_preconditions(ctx, "mvs_sweep_run_band", view_first, view_count, flags, vol, fused))) return rc;
     for (int d = 0; d < ctx->D; d++)
         if (!(ctx->z_host[d] > -1.0f && ctx->z_host[d] < 1.0f))
             return fail(ctx, MVS_ESTATE, "mvs_sweep_run_band: the plane table holds the band's offsets and must lie inside (-1, 1): offset %d is %g", d, ctx->z_host[d]);
-    if (view_first < 0 || view_count < 0 || view_first + view_count > ctx->V)
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: view range [%d,%d) outside 0..%d", view_first, view_first + view_count, ctx->V);
-    if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: the fixed sampler's cells hold at most 255 views (have %d)", ctx->V);
-    if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: the fixed sampler addresses images of up to 16383 x 16383");
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)ctx->W * ctx->H;
-    int rc;
     if ((rc = sweep_outputs(ctx, vol, "mvs_sweep_run_band"))) return rc;
     if ((rc = ensure(ctx, ctx->band_prior, P * sizeof(float)))) return rc;
     if ((rc = ensure_fx_lut(ctx))) return rc;
@@ -187,12 +178,7 @@ int mvs_sweep_run_band(mvs_ctx *ctx, int view_first, int view_count, const void 
     MVS_HIP(ctx, hipGetLastError());
     ctx->band_planes = ctx->D;
     ctx->band_resolved = false;
-    if (fused) {
-        note_full_selection(ctx);
-    } else {   // the index map is no selection on this volume: refinement, cleaning and the resolve wait for one (mvs_sweep_argmin, ...)
-        ctx->sel_planes = 0;
-        ctx->sel_band_planes = 0;
-    }
+    fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }
 

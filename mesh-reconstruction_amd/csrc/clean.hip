@@ -278,7 +278,7 @@ int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int spe
     if (!ctx->index.ptr || !ctx->depth.ptr || !ctx->cost.ptr || !ctx->sel_planes)
         return fail(ctx, MVS_ESTATE, "mvs_sweep_clean: no depth selection yet (mvs_sweep_run with MVS_SWEEP_FUSED_ARGMIN, mvs_sweep_argmin or mvs_sweep_aggregate)");
     const int W = ctx->W, H = ctx->H, D = ctx->D;
-    if (ctx->sel_planes != D)   // rules 1 and 2 read the volume (and S) at the selected plane
+    if (!selection_current(ctx))   // rules 1 and 2 read the volume (and S) at the selected plane
         return fail(ctx, MVS_ESTATE, "mvs_sweep_clean: the depth selection was made over %d planes, the context now has %d (select again)", ctx->sel_planes, D);
     const size_t P = (size_t)W * H;
     if (P > (size_t)INT_MAX) return fail(ctx, MVS_EINVAL, "mvs_sweep_clean: %zu pixels do not fit the 32-bit labels", P);
@@ -286,7 +286,7 @@ int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int spe
     const uint32_t *vol;
     size_t vol_bytes;
     if (int rc = reader_volume(ctx, "mvs_sweep_clean", vol, vol_bytes)) return rc;
-    const bool have_volume = ctx->have_planes && vol && vol_bytes >= P * (size_t)D * sizeof(uint32_t);
+    const bool have_volume = volume_holds_planes(ctx, vol, vol_bytes);
     // min_views 1 rejects a selected cell that no view sees; the library selects none, so without a volume there is nothing to test
     const bool rule1 = min_views >= 2 || (min_views == 1 && have_volume), rule2 = uniqueness_percent > 0, rule3 = speckle_min_size > 0;
     if ((rule1 || rule2) && !have_volume)
@@ -312,16 +312,14 @@ int mvs_sweep_clean(mvs_ctx *ctx, int min_views, int uniqueness_percent, int spe
     MVS_HIP(ctx, hipMemsetAsync(counters, 0, 4 * sizeof(unsigned), ctx->stream));
     if (rule1 || rule2) {
         const uint16_t *S = (const uint16_t *)ctx->agg_sum.ptr;
-        const bool fx = ctx->sampler == MVS_SAMPLER_FIXED;
         const uint32_t mv = (uint32_t)min_views, u = (uint32_t)uniqueness_percent;
-        if (fx && agg)
-            clean_rules_kernel<CS_FIXED, true><<<pblocks, 256, 0, ctx->stream>>>(S, vol, P, D, rule1, mv, u, depth, cost, index, counters);
-        else if (fx)
-            clean_rules_kernel<CS_FIXED, false><<<pblocks, 256, 0, ctx->stream>>>(nullptr, vol, P, D, rule1, mv, u, depth, cost, index, counters);
-        else if (agg)
-            clean_rules_kernel<CS_EXACT, true><<<pblocks, 256, 0, ctx->stream>>>(S, vol, P, D, rule1, mv, u, depth, cost, index, counters);
-        else
-            clean_rules_kernel<CS_EXACT, false><<<pblocks, 256, 0, ctx->stream>>>(nullptr, vol, P, D, rule1, mv, u, depth, cost, index, counters);
+        with_cells(ctx, [&](auto cs) {
+            constexpr int CS = decltype(cs)::value;
+            if (agg)
+                clean_rules_kernel<CS, true><<<pblocks, 256, 0, ctx->stream>>>(S, vol, P, D, rule1, mv, u, depth, cost, index, counters);
+            else
+                clean_rules_kernel<CS, false><<<pblocks, 256, 0, ctx->stream>>>(nullptr, vol, P, D, rule1, mv, u, depth, cost, index, counters);
+        });
     } else {
         clean_count_kernel<<<pblocks, 256, 0, ctx->stream>>>(index, P, counters);
     }

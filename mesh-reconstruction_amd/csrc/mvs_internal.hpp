@@ -49,10 +49,10 @@ struct mvs_ctx {
     size_t volume_bytes = 0;
     bool volume_external = false;
     mvs::DevBuf depth, cost, index;  // H*W each
-    int sel_planes = 0;              // plane count EVERY row of the index map was last selected over (0: no depth selection yet); set by the host
-                                     // entries that launch a writer of `index`, compared with D by mvs_sweep_refine_depth and mvs_sweep_clean
+    int sel_planes = 0;              // plane count EVERY row of the index map was last selected over (0: no depth selection); set by the note_*
+                                     // transitions below only, compared with D by the readers of the index map (selection_current)
     int sel_band_planes = 0;         // fused row-band runs over a plane count other than sel_planes: that count and the rows [lo, hi) the
-    int sel_band_lo = 0, sel_band_hi = 0;  // bands cover so far; sel_planes follows when they cover all rows (sweep.hip: note_selection)
+    int sel_band_lo = 0, sel_band_hi = 0;  // bands cover so far; sel_planes follows when they cover all rows (note_rows_selected)
     int pad_pitch = 0;
     size_t pad_slab = 0;             // bytes per padded side image
     int V = 0, D = 0;
@@ -263,16 +263,29 @@ int tsdf_ensure_appearance(mvs_ctx *ctx);
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
-// window.hip: the packed volume the readers of mvs_sweep_set_volume_source read -- the raw volume as the context holds it (pointer and size
-// may be null / short: the reader's own checks apply, as before), or Wv; MVS_ESTATE under MVS_VOLUME_WINDOWED without a Wv of the current planes
+// select.hip: the packed volume the readers of mvs_sweep_set_volume_source read -- the raw volume as the context holds it (pointer and size
+// may be null / short: the reader's own checks apply), or Wv; MVS_ESTATE under MVS_VOLUME_WINDOWED without a Wv of the current planes
 int reader_volume(mvs_ctx *ctx, const char *who, const uint32_t *&vol, size_t &bytes);
 
-// a writer of every row of ctx->index has been launched over the current planes (mvs_ctx::sel_planes)
+// what the readers test next, each with its own refusal: the bytes a packed volume of the current planes takes, whether (vol, bytes) is
+// one, and whether the index map is a selection over the current planes
+inline size_t volume_need(const mvs_ctx *ctx) { return (size_t)ctx->W * ctx->H * (size_t)ctx->D * sizeof(uint32_t); }
+inline bool volume_holds_planes(const mvs_ctx *ctx, const uint32_t *vol, size_t bytes) { return ctx->have_planes && vol && bytes >= volume_need(ctx); }
+inline bool selection_current(const mvs_ctx *ctx) { return ctx->sel_planes == ctx->D; }
+
+// The selection state (sel_planes, sel_band_*, band_planes) changes through these transitions only.
+// A writer of every row of ctx->index has been launched over the current planes:
 inline void note_full_selection(mvs_ctx *ctx)
 {
     ctx->sel_planes = ctx->D;
     ctx->sel_band_planes = 0;
 }
+// a fused run has rewritten rows [r0, r1) of the index map over the current planes (select.hip):
+void note_rows_selected(mvs_ctx *ctx, int r0, int r1);
+// the volume was rewritten without a selection on it: refinement, cleaning and the band resolve wait for one (mvs_sweep_argmin, ...)
+inline void note_no_selection(mvs_ctx *ctx) { ctx->sel_planes = ctx->sel_band_planes = 0; }
+// an ordinary sweep has run: the volume and the maps stop being a band run's (mvs_sweep_band_resolve refuses from here on)
+inline void note_ordinary_sweep(mvs_ctx *ctx) { ctx->band_planes = 0; }
 
 // the sweep's input setters with the final synchronisation optional (context.hip; mvs_sweep queues all of them and waits once)
 int sweep_set_main_impl(mvs_ctx *ctx, const float main_cam[16], const uint8_t *main_hw, bool sync, bool device = false);

@@ -1,10 +1,10 @@
-// sweep.hip -- plane-sweep photometric cost volume + per-pixel depth selection for gfx950 (MI355X).
+// sweep.hip -- plane-sweep photometric cost volume for gfx950 (MI355X): the exact sampler, the run dispatch and the one-call mvs_sweep.
 //
 // What it replaces: the reference evaluates ONE depth hypothesis per pixel per (main, side) pair by
 // rasterising the proxy mesh and running shader.frag:11-25 (projective texture fetch + in-frame test)
 // followed by an RGB8 read-back (render_glx.cpp:261-367).  This file evaluates the same fragment
 // program at D synthetic positions pos_d = main^-1 * (x_ndc, y_ndc, z_d, 1) per pixel and V side
-// views, accumulates |I_main - I_warp| and picks the best plane.
+// views and accumulates |I_main - I_warp|; select.hip picks the best plane.
 //
 // Arithmetic contract (identical in oracle/sweep_oracle.c; DESIGN.md "sweep arithmetic"):
 //   s      = fma(z, B, A)            A = fma(Q0, xn, fma(Q1, yn, Q3)), B = Q2  (per row of Q)
@@ -20,7 +20,6 @@
 //   plan_regions      per (tile, plane chunk, view): bounding box of the warped tile -> LDS region
 //   sweep_tiled       LDS-staged side-image tiles; 64x8-pixel tiles x 32 planes or 64x16 x 16 planes per chunk
 //   sweep_generic     no tiling, global gathers; any geometry; also the in-kernel fallback
-//   argmin_volume     depth selection over the packed volume (after an optional cross-rank reduction)
 #include "sweep_shared.hpp"
 
 #include <cstdlib>
@@ -557,128 +556,6 @@ __global__ __launch_bounds__(256, 3) void sweep_tiled(SweepParams p)
     }
 }
 
-// Sub-plane refinement of the selected depth: parabola through the mean costs of the selected plane and its
-// two neighbours, f32 with one rounding per operation -- oracle/sweep_oracle.c: orc_refine_depth states the arithmetic.
-template <int CS>
-__global__ __launch_bounds__(256) void refine_depth(const uint32_t *__restrict__ vol, size_t P, int D, const float *__restrict__ z, const int *__restrict__ index,
-                                                    float *__restrict__ depth)
-{
-    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    const int i = index[p];
-    if (i < 0) {
-        depth[p] = MVS_BACKGROUND_DEPTH;
-        return;
-    }
-    constexpr uint32_t M = (1u << CS) - 1u;
-    float zr = z[i];
-    if (i > 0 && i < D - 1) {
-        const uint32_t a = vol[(size_t)(i - 1) * P + p], b = vol[(size_t)i * P + p], c = vol[(size_t)(i + 1) * P + p];
-        if ((a >> CS) != 0u && (c >> CS) != 0u && (b >> CS) != 0u) {
-            const float ca = (float)(a & M) / (float)(a >> CS), cb = (float)(b & M) / (float)(b >> CS), cc = (float)(c & M) / (float)(c >> CS);
-            const float den = (ca - 2.0f * cb) + cc;
-            if (den > 0.0f) {
-                float t = (0.5f * (ca - cc)) / den;
-                t = t < -0.5f ? -0.5f : (t > 0.5f ? 0.5f : t);
-                zr = t >= 0.0f ? __builtin_fmaf(t, z[i + 1] - z[i], z[i]) : __builtin_fmaf(-t, z[i - 1] - z[i], z[i]);
-            }
-        }
-    }
-    depth[p] = zr;
-}
-
-// merge of the partial bests of a plane-split launch: splits are in ascending plane order and a later split wins only
-// if strictly better, so ties still go to the lowest plane
-template <int CS>
-__global__ __launch_bounds__(256) void combine_best(SweepParams p, int nsplit, size_t pix_first, size_t pix_count)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= pix_count) return;
-    const size_t pix = pix_first + i, P = (size_t)p.W * p.H;
-    uint32_t best = 0u;
-    int bi = -1;
-    for (int s = 0; s < nsplit; s++) {
-        const uint2 st = p.part[(size_t)s * P + pix];
-        argmin_update_packed<CS>(st.x, (int)st.y, best, bi);
-    }
-    store_best<CS>(p, pix, best & ((1u << CS) - 1u), best >> CS, bi);
-}
-
-// host: that merge for a launch whose splits (choose_split) left their partial bests in p.part, over the launch's rows
-template <int CS>
-static int merge_split_bests(mvs_ctx *ctx, const SweepParams &p)
-{
-    if (!p.part) return MVS_OK;
-    const size_t first = (size_t)p.row_begin * p.W;
-    const size_t count = (size_t)(p.row_end - p.row_begin) * p.W;
-    combine_best<CS><<<(unsigned)((count + 255) / 256), 256, 0, ctx->stream>>>(p, split_count(p), first, count);
-    MVS_HIP(ctx, hipGetLastError());
-    return MVS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// depth selection over the packed volume
-// ------------------------------------------------------------------------------------------------------
-// Layout [D][P] keeps a pixel on a lane, so the reduction over planes runs in registers; each thread
-// streams 16-byte loads of 4 consecutive pixels per plane (P % 4 == 0) or single cells otherwise.
-// part != nullptr: `vol` holds planes [d_first, d_first + D) only (the slice a rank owns after a reduce-scatter) and the result
-// is the partial selection (best packed cell, best ABSOLUTE plane index) per pixel, to be merged by combine_best
-template <int VEC, int CS>
-__global__ __launch_bounds__(256) void argmin_volume(const uint32_t *__restrict__ vol, size_t P, int D,
-                                                     const float *__restrict__ z, float *__restrict__ depth,
-                                                     float *__restrict__ cost, int *__restrict__ index,
-                                                     uint2 *__restrict__ part = nullptr, int d_first = 0)
-{
-    const size_t base = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
-    if (base >= P) return;
-    uint32_t bs[VEC], bc[VEC];
-    int bi[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; i++) {
-        bs[i] = 0u;
-        bc[i] = 0u;
-        bi[i] = -1;
-    }
-    int d = 0;
-    constexpr int UNR = 8;  // planes in flight per thread: 8 x 16 B, non-temporal (the stream is read once): 4.75 -> 5.64 TB/s at c3
-    for (; d + UNR <= D; d += UNR) {
-        uint32_t c[UNR][VEC];
-#pragma unroll
-        for (int u = 0; u < UNR; u++) {
-            if (VEC == 4) {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 t = __builtin_nontemporal_load((const u32x4 *)(vol + (size_t)(d + u) * P + base));
-                c[u][0] = t.x;
-                c[u][1 % VEC] = t.y;
-                c[u][2 % VEC] = t.z;
-                c[u][3 % VEC] = t.w;
-            } else {
-                c[u][0] = vol[(size_t)(d + u) * P + base];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; u++)
-#pragma unroll
-            for (int i = 0; i < VEC; i++) argmin_update<CS>(c[u][i], d + u, bs[i], bc[i], bi[i]);
-    }
-    for (; d < D; d++) {
-#pragma unroll
-        for (int i = 0; i < VEC; i++) argmin_update<CS>(vol[(size_t)d * P + base + i], d, bs[i], bc[i], bi[i]);
-    }
-    if (part) {
-#pragma unroll
-        for (int i = 0; i < VEC; i++)
-            part[base + i] = bi[i] >= 0 ? make_uint2((bc[i] << CS) | bs[i], (uint32_t)(bi[i] + d_first)) : make_uint2(0u, 0xffffffffu);
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < VEC; i++) {
-        depth[base + i] = bi[i] >= 0 ? z[bi[i]] : MVS_BACKGROUND_DEPTH;
-        cost[base + i] = bi[i] >= 0 ? cell_cost<CS>(bs[i], bc[i]) : __builtin_inff();
-        index[base + i] = bi[i];
-    }
-}
-
 // the sweep's sampler at one plane per pixel, z = depth[p] (parity hook)
 __global__ __launch_bounds__(256) void warp_by_depth_kernel(const float *__restrict__ depth, const float *__restrict__ Q,
                                                             const uint8_t *__restrict__ pad, int pitch, int W, int H,
@@ -698,16 +575,6 @@ __global__ __launch_bounds__(256) void warp_by_depth_kernel(const float *__restr
     }
     out2[2 * pix] = (uint8_t)(cell & 0xffu);
     out2[2 * pix + 1] = cell ? 255 : 0;
-}
-
-template <int CS>
-__global__ void unpack_volume(const uint32_t *__restrict__ vol, float *__restrict__ out, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t cell = vol[i];
-    const uint32_t s = cell & ((1u << CS) - 1u), c = cell >> CS;
-    out[i] = c ? cell_cost<CS>(s, c) : __builtin_inff();
 }
 
 // exhaustive self-check helper for the reciprocal (tests): out[0] counts w where rcp_rn(w) != 1.0f/w
@@ -749,53 +616,12 @@ int mvs_sweep_use_volume(mvs_ctx *ctx, void *device_ptr, size_t bytes)
     return MVS_OK;
 }
 
-static int ensure_outputs(mvs_ctx *ctx, bool need_volume)
-{
-    const size_t P = (size_t)ctx->W * ctx->H;
-    int rc;
-    if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->cost, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->index, P * sizeof(int)))) return rc;
-    if (need_volume) {
-        const size_t need = P * (size_t)ctx->D * sizeof(uint32_t);
-        if (ctx->volume_external) {
-            if (ctx->volume_bytes < need)
-                return fail(ctx, MVS_EINVAL, "caller volume is %zu bytes, need %zu", ctx->volume_bytes, need);
-        } else {
-            if ((rc = ensure(ctx, ctx->volume_own, need))) return rc;
-            ctx->volume = (uint32_t *)ctx->volume_own.ptr;
-            ctx->volume_bytes = ctx->volume_own.bytes;
-        }
-    }
-    return MVS_OK;
-}
-
 // the views, planes and rows of one sweep call
 struct SweepRange {
     int view_first, view_count, plane_first, plane_count, row_first, row_count;
 };
 
 static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags);
-
-// a fused run has rewritten rows [r0, r1) of the index map over the current planes.  The whole image, or bands over the plane count the
-// map already has, leave a selection over D planes; bands over another count leave one only once they -- each overlapping or touching
-// what the earlier ones covered -- reach every row: until then the other rows hold planes of the old count and there is no selection
-static void note_selection(mvs_ctx *ctx, int r0, int r1)
-{
-    const int D = ctx->D;
-    if (r0 <= 0 && r1 >= ctx->H) return note_full_selection(ctx);
-    if (ctx->sel_planes == D) return;
-    ctx->sel_planes = 0;  // rows of two plane counts: no selection until the bands are through
-    if (ctx->sel_band_planes != D || r0 > ctx->sel_band_hi || r1 < ctx->sel_band_lo) {
-        ctx->sel_band_planes = D;
-        ctx->sel_band_lo = r0;
-        ctx->sel_band_hi = r1;
-    } else {
-        ctx->sel_band_lo = r0 < ctx->sel_band_lo ? r0 : ctx->sel_band_lo;
-        ctx->sel_band_hi = r1 > ctx->sel_band_hi ? r1 : ctx->sel_band_hi;
-    }
-    if (ctx->sel_band_lo <= 0 && ctx->sel_band_hi >= ctx->H) note_full_selection(ctx);
-}
 
 int mvs_sweep_run(mvs_ctx *ctx, int view_first, int view_count, unsigned flags)
 {
@@ -920,7 +746,7 @@ static int sweep_run_fixed(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &
     narrow_params(p, r.plane_first, r.plane_count, r.row_first, r.row_count);
     ProfileScope ps(ctx, MVS_K_SWEEP);
     if ((rc = rect ? sweep_rect_launch(ctx, p, f) : sweep_fx_launch(ctx, p, f))) return rc;
-    return merge_split_bests<CS_FIXED>(ctx, p);
+    return merge_split_bests(ctx, p);
 }
 
 static int sweep_run_exact(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &f)
@@ -949,7 +775,7 @@ static int sweep_run_exact(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &
         narrow_params(p, r.plane_first, r.plane_count, r.row_first, r.row_count);
         ProfileScope ps(ctx, MVS_K_SWEEP);
         if ((rc = sweep_xrect_launch(ctx, p, f))) return rc;
-        if ((rc = merge_split_bests<CS_EXACT>(ctx, p))) return rc;
+        if ((rc = merge_split_bests(ctx, p))) return rc;
         ctx->exact_last_shape = 5;
         return MVS_OK;
     }
@@ -989,7 +815,7 @@ static int sweep_run_exact(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &
     narrow_params(p, r.plane_first, r.plane_count, r.row_first, r.row_count);
     ProfileScope ps(ctx, MVS_K_SWEEP);
     if ((rc = sweep_tiled_launch(ctx, p, f))) return rc;
-    return merge_split_bests<CS_EXACT>(ctx, p);
+    return merge_split_bests(ctx, p);
 }
 
 static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags)
@@ -1013,120 +839,20 @@ static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags)
     f.forced_split = (int)((flags >> 16) & 0xff);  // forced split count for timing experiments
     if (!f.vol && !f.fused) return fail(ctx, MVS_EINVAL, "mvs_sweep_run: flags select neither volume nor fused argmin");
     MVS_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_outputs(ctx, f.vol);
+    int rc = sweep_outputs(ctx, f.vol, "mvs_sweep_run");
     if (rc) return rc;
     if (r.row_count <= 0 || r.plane_count <= 0) return MVS_OK;  // empty band or empty plane group: nothing to compute
-    ctx->band_planes = 0;  // the volume and the maps stop being a band run's (band.hip: mvs_sweep_band_resolve refuses from here on)
+    note_ordinary_sweep(ctx);
     rc = ctx->sampler == MVS_SAMPLER_FIXED ? sweep_run_fixed(ctx, r, f) : sweep_run_exact(ctx, r, f);
-    if (rc == MVS_OK && f.fused) note_selection(ctx, r.row_first, r.row_first + r.row_count);
+    if (rc == MVS_OK && f.fused) note_rows_selected(ctx, r.row_first, r.row_first + r.row_count);
     return rc;
-}
-
-// depth selection over `vol` with the cell layout of the context's sampler; 16-byte loads when the pixel count and the pointer allow
-static void launch_argmin(mvs_ctx *ctx, const uint32_t *vol, size_t P, int D, const float *z, float *depth, float *cost, int *index, uint2 *part,
-                          int d_first)
-{
-    const bool wide = P % 4 == 0 && ((uintptr_t)vol % 16) == 0;
-    const unsigned blocks = (unsigned)(((wide ? P / 4 : P) + 255) / 256);
-    const bool fx = ctx->sampler == MVS_SAMPLER_FIXED;
-    if (wide && fx)
-        argmin_volume<4, CS_FIXED><<<blocks, 256, 0, ctx->stream>>>(vol, P, D, z, depth, cost, index, part, d_first);
-    else if (wide)
-        argmin_volume<4, CS_EXACT><<<blocks, 256, 0, ctx->stream>>>(vol, P, D, z, depth, cost, index, part, d_first);
-    else if (fx)
-        argmin_volume<1, CS_FIXED><<<blocks, 256, 0, ctx->stream>>>(vol, P, D, z, depth, cost, index, part, d_first);
-    else
-        argmin_volume<1, CS_EXACT><<<blocks, 256, 0, ctx->stream>>>(vol, P, D, z, depth, cost, index, part, d_first);
-}
-
-int mvs_sweep_argmin(mvs_ctx *ctx)
-{
-    if (!ctx) return MVS_EINVAL;
-    const uint32_t *vol;
-    size_t vol_bytes;
-    int rc = reader_volume(ctx, "mvs_sweep_argmin", vol, vol_bytes);   // refuses before anything is allocated
-    if (rc) return rc;
-    const bool raw = ctx->volume_source == MVS_VOLUME_RAW;
-    if (raw && (!ctx->have_planes || !ctx->volume))
-        return fail(ctx, MVS_ESTATE, "mvs_sweep_argmin: no cost volume (run mvs_sweep_run with MVS_SWEEP_VOLUME)");
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_outputs(ctx, raw))) return rc;
-    if (raw) vol = ctx->volume;   // (ensure_outputs may have re-made the context's own)
-    const size_t P = (size_t)ctx->W * ctx->H;
-    ProfileScope ps(ctx, MVS_K_ARGMIN);
-    launch_argmin(ctx, vol, P, ctx->D, (const float *)ctx->ztab.ptr, (float *)ctx->depth.ptr, (float *)ctx->cost.ptr, (int *)ctx->index.ptr,
-                  nullptr, 0);
-    MVS_HIP(ctx, hipGetLastError());
-    note_full_selection(ctx);
-    return MVS_OK;
-}
-
-int mvs_sweep_refine_depth(mvs_ctx *ctx)
-{
-    if (!ctx) return MVS_EINVAL;
-    const uint32_t *vol;
-    size_t vol_bytes;
-    if (int rc = reader_volume(ctx, "mvs_sweep_refine_depth", vol, vol_bytes)) return rc;
-    if (!ctx->have_planes || !vol || !ctx->index.ptr || !ctx->sel_planes)
-        return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: needs the packed volume and a depth selection (MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN, or mvs_sweep_argmin)");
-    // the kernel reads z[index] and the cells of planes index - 1 .. index + 1: the index map must be one over the current planes ...
-    if (ctx->sel_planes != ctx->D)
-        return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: the depth selection was made over %d planes, the context now has %d (select again)", ctx->sel_planes, ctx->D);
-    // ... and the volume must hold them (ensure_outputs and mvs_sweep_aggregate refuse the same)
-    const size_t P = (size_t)ctx->W * ctx->H, need = P * (size_t)ctx->D * sizeof(uint32_t);
-    if (vol_bytes < need) {
-        if (ctx->volume_external) return fail(ctx, MVS_EINVAL, "mvs_sweep_refine_depth: caller volume is %zu bytes, %d planes need %zu", vol_bytes, ctx->D, need);
-        return fail(ctx, MVS_ESTATE, "mvs_sweep_refine_depth: the context's volume is %zu bytes, %d planes need %zu (mvs_sweep_run with MVS_SWEEP_VOLUME)", vol_bytes, ctx->D, need);
-    }
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->sampler == MVS_SAMPLER_FIXED)
-        refine_depth<CS_FIXED><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(vol, P, ctx->D, (const float *)ctx->ztab.ptr, (const int *)ctx->index.ptr, (float *)ctx->depth.ptr);
-    else
-        refine_depth<CS_EXACT><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(vol, P, ctx->D, (const float *)ctx->ztab.ptr, (const int *)ctx->index.ptr, (float *)ctx->depth.ptr);
-    MVS_HIP(ctx, hipGetLastError());
-    return MVS_OK;
-}
-
-int mvs_sweep_argmin_partial(mvs_ctx *ctx, const void *volume_slice_dev, int plane_first, int plane_count, void *partial_out_dev)
-{
-    if (!ctx || !volume_slice_dev || !partial_out_dev) return fail(ctx, MVS_EINVAL, "mvs_sweep_argmin_partial: null argument");
-    if (!ctx->have_planes) return fail(ctx, MVS_ESTATE, "mvs_sweep_argmin_partial: set the planes first");
-    if (plane_first < 0 || plane_count <= 0 || plane_first + plane_count > ctx->D)
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_argmin_partial: planes [%d,%d) outside 0..%d", plane_first, plane_first + plane_count, ctx->D);
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t P = (size_t)ctx->W * ctx->H;
-    ProfileScope ps(ctx, MVS_K_ARGMIN);
-    launch_argmin(ctx, (const uint32_t *)volume_slice_dev, P, plane_count, nullptr, nullptr, nullptr, nullptr, (uint2 *)partial_out_dev, plane_first);
-    MVS_HIP(ctx, hipGetLastError());
-    return MVS_OK;
-}
-
-int mvs_sweep_combine_partials(mvs_ctx *ctx, const void *partials_dev, int nparts)
-{
-    if (!ctx || !partials_dev || nparts <= 0) return fail(ctx, MVS_EINVAL, "mvs_sweep_combine_partials: bad argument");
-    if (!ctx->have_planes) return fail(ctx, MVS_ESTATE, "mvs_sweep_combine_partials: set the planes first");
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_outputs(ctx, false);
-    if (rc) return rc;
-    SweepParams p;
-    fill_params(ctx, p, 0, 0, 16, 16);
-    p.part = (uint2 *)partials_dev;  // read-only here
-    const size_t P = (size_t)ctx->W * ctx->H;
-    ProfileScope ps(ctx, MVS_K_ARGMIN);
-    if (ctx->sampler == MVS_SAMPLER_FIXED)
-        combine_best<CS_FIXED><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(p, nparts, 0, P);
-    else
-        combine_best<CS_EXACT><<<(unsigned)((P + 255) / 256), 256, 0, ctx->stream>>>(p, nparts, 0, P);
-    MVS_HIP(ctx, hipGetLastError());
-    note_full_selection(ctx);
-    return MVS_OK;
 }
 
 void *mvs_sweep_volume_device(mvs_ctx *ctx, size_t *bytes)
 {
     if (!ctx || !ctx->have_planes) return nullptr;
-    if (ensure_outputs(ctx, true) != MVS_OK) return nullptr;
-    if (bytes) *bytes = (size_t)ctx->W * ctx->H * (size_t)ctx->D * sizeof(uint32_t);
+    if (sweep_outputs(ctx, true, "mvs_sweep_volume_device") != MVS_OK) return nullptr;
+    if (bytes) *bytes = volume_need(ctx);
     return ctx->volume;
 }
 
@@ -1422,11 +1148,7 @@ int mvs_sweep(mvs_ctx *ctx, const float main_cam[16], const uint8_t *main_hw, in
     if (volume_dhw) {
         const size_t n = (size_t)ctx->W * ctx->H * (size_t)nplanes;
         if ((rc = ensure(ctx, ctx->r_tmp0, n * sizeof(float)))) return rc;
-        if (ctx->sampler == MVS_SAMPLER_FIXED)
-            unpack_volume<CS_FIXED><<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(ctx->volume, (float *)ctx->r_tmp0.ptr, n);
-        else
-            unpack_volume<CS_EXACT><<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(ctx->volume, (float *)ctx->r_tmp0.ptr, n);
-        MVS_HIP(ctx, hipGetLastError());
+        if ((rc = unpack_volume_launch(ctx, ctx->volume, (float *)ctx->r_tmp0.ptr, n))) return rc;
         MVS_HIP(ctx, hipMemcpyAsync(volume_dhw, ctx->r_tmp0.ptr, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }

@@ -1074,7 +1074,7 @@ int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f)
 {
     RectTables rt;
     rect_tables(ctx, p, rt);
-    // the cold block follows the tables; its output pointers can change between plan and launch (ensure_outputs): re-sent when they do
+    // the cold block follows the tables; its output pointers can change between plan and launch (sweep_outputs): re-sent when they do
     RectCold *cold_dev = (RectCold *)((uint32_t *)ctx->rect_tab.ptr + rect_table_dwords(p));
     RectCold cold;
     memcpy(&cold, ctx->rect_cold_host.data(), sizeof(RectCold));

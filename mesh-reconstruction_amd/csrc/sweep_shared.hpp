@@ -1,16 +1,15 @@
 // sweep_shared.hpp -- what the two sweep samplers (sweep.hip: exact f32, contract v1; sweep_fx.hip: fixed point, contract v2)
-// have in common: launch parameters, the projective arithmetic up to s and r = RN(1/s.w), the XCD-aware tile order and the
-// packed-cell helpers.  Cells are  count << CS | sum  with CS = 16 (exact sampler: sum of |u8 - u8|, <= 257 views) or
-// CS = 24 (fixed sampler: sum of |weights.texels - 255 I_main|, <= 255 views).
+// have in common: launch parameters, the projective arithmetic up to s and r = RN(1/s.w), the XCD-aware tile order, and the host-side
+// decisions every sweep entry makes alike (outputs, cell layout, the fixed-point entries' preconditions).  The packed cells and the rules
+// of depth selection are select_rules.hpp's.
 #pragma once
 #include "mvs_internal.hpp"
+#include "select_rules.hpp"
 
 #include <climits>
 #include <type_traits>
 
 namespace mvs {
-
-constexpr int CS_EXACT = 16, CS_FIXED = 24;
 
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 
@@ -109,38 +108,6 @@ __device__ __forceinline__ Affine view_affine(const float *__restrict__ q, float
     return a;
 }
 
-// HIP declares __umul24 as returning int: compared as such, products >= 2^31 (fixed sampler, > 181 views at maximal cost) would order wrongly
-__device__ __forceinline__ uint32_t umul24u(uint32_t a, uint32_t b) { return (uint32_t)__umul24(a, b); }
-
-// running best plane: s/c < bs/bc  <=>  s*bc < bs*c; the products stay below 2^32 (s < 2^16, c < 2^16 or s < 2^24, c < 2^8)
-template <int CS = CS_EXACT>
-__device__ __forceinline__ void argmin_update(uint32_t cell, int d, uint32_t &bs, uint32_t &bc, int &bi)
-{
-    const uint32_t s = cell & ((1u << CS) - 1u), c = cell >> CS;  // s < 2^24, c < 2^16: the 24-bit multiplies below are exact
-    const bool better = (c != 0u) && (bi < 0 || umul24u(s, bc) < umul24u(bs, c));
-    bs = better ? s : bs;
-    bc = better ? c : bc;
-    bi = better ? d : bi;
-}
-
-// the same with the best (count, sum) kept as one packed cell: two registers of state per pixel
-template <int CS = CS_EXACT>
-__device__ __forceinline__ void argmin_update_packed(uint32_t cell, int d, uint32_t &best, int &bi)
-{
-    constexpr uint32_t M = (1u << CS) - 1u;
-    const uint32_t s = cell & M, c = cell >> CS, bs = best & M, bc = best >> CS;
-    const bool better = (c != 0u) && (bi < 0 || umul24u(s, bc) < umul24u(bs, c));
-    best = better ? cell : best;
-    bi = better ? d : bi;
-}
-
-// mean cost in grey levels: sum / count (exact sampler) or sum / (255 count) (fixed sampler: sums are in 1/255 grey levels)
-template <int CS = CS_EXACT>
-__device__ __forceinline__ float cell_cost(uint32_t bs, uint32_t bc)
-{
-    return CS == CS_EXACT ? (float)bs / (float)bc : (float)bs / (float)(255u * bc);
-}
-
 template <int CS = CS_EXACT>
 __device__ __forceinline__ void store_best(const SweepParams &p, size_t pix, uint32_t bs, uint32_t bc, int bi)
 {
@@ -231,22 +198,49 @@ inline int fill_params(mvs_ctx *ctx, SweepParams &p, int v0, int vcount, int til
     return MVS_OK;
 }
 
-// host: the maps and, for a volume run, the packed volume of the current planes (what sweep.hip's ensure_outputs gives mvs_sweep_run), for the
-// sweep entry points outside sweep.hip; a caller's volume that is too small is refused before anything is allocated
+// host: the depth / cost / index maps every writer of a selection needs
+inline int ensure_maps(mvs_ctx *ctx)
+{
+    const size_t P = (size_t)ctx->W * ctx->H;
+    int rc;
+    if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
+    if ((rc = ensure(ctx, ctx->cost, P * sizeof(float)))) return rc;
+    return ensure(ctx, ctx->index, P * sizeof(int));
+}
+
+// host: the maps and, for a volume run, the packed volume of the current planes; a caller's volume that is too small is refused before
+// anything is allocated
 inline int sweep_outputs(mvs_ctx *ctx, bool need_volume, const char *who)
 {
-    const size_t P = (size_t)ctx->W * ctx->H, need = P * (size_t)ctx->D * sizeof(uint32_t);
+    const size_t need = volume_need(ctx);
     int rc;
     if (need_volume && ctx->volume_external && ctx->volume_bytes < need)
         return fail(ctx, MVS_EINVAL, "%s: caller volume is %zu bytes, need %zu", who, ctx->volume_bytes, need);
-    if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->cost, P * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->index, P * sizeof(int)))) return rc;
+    if ((rc = ensure_maps(ctx))) return rc;
     if (need_volume && !ctx->volume_external) {
         if ((rc = ensure(ctx, ctx->volume_own, need))) return rc;
         ctx->volume = (uint32_t *)ctx->volume_own.ptr;
         ctx->volume_bytes = ctx->volume_own.bytes;
     }
+    return MVS_OK;
+}
+
+// host: what mvs_sweep_run_band and mvs_sweep_run_zncc (`who`) check alike before they touch anything: the flag bits, the inputs, the
+// sampler and its limits, the view range.  Decodes the two output flags.
+inline int fx_sweep_preconditions(mvs_ctx *ctx, const char *who, int view_first, int view_count, unsigned flags, bool &vol, bool &fused)
+{
+    if (flags & ~(MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN))
+        return fail(ctx, MVS_EINVAL, "%s: unknown flag bits 0x%x (MVS_SWEEP_VOLUME and MVS_SWEEP_FUSED_ARGMIN only)", who,
+                    flags & ~(MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN));
+    vol = (flags & MVS_SWEEP_VOLUME) != 0;
+    fused = (flags & MVS_SWEEP_FUSED_ARGMIN) != 0;
+    if (!vol && !fused) return fail(ctx, MVS_EINVAL, "%s: flags select neither volume nor fused argmin", who);
+    if (!ctx->have_main || !ctx->have_views || !ctx->have_planes) return fail(ctx, MVS_ESTATE, "%s: set main view, side views and planes first", who);
+    if (ctx->sampler != MVS_SAMPLER_FIXED) return fail(ctx, MVS_ESTATE, "%s: implemented for MVS_SAMPLER_FIXED (the library default)", who);
+    if (view_first < 0 || view_count < 0 || view_first + view_count > ctx->V)
+        return fail(ctx, MVS_EINVAL, "%s: view range [%d,%d) outside 0..%d", who, view_first, view_first + view_count, ctx->V);
+    if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler's cells hold at most 255 views (have %d)", who, ctx->V);
+    if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler addresses images of up to 16383 x 16383", who);
     return MVS_OK;
 }
 
@@ -270,7 +264,7 @@ inline int split_count(const SweepParams &p) { return div_up(p.chunk1 - p.chunk0
 // host: the plane split of a tiled launch whose ranges are set.  A launch with too few tiles to fill the chip hands each workgroup
 // p.cps of a tile's plane chunks (blockIdx.y selects them), aiming at `wgs_per_cu` workgroups per CU unless an experiment forces the
 // split count; `max_cps` bounds what one workgroup can take.  With a fused depth selection the splits' partial bests go to p.part,
-// for merge_split_bests (sweep.hip).
+// for merge_split_bests.
 inline int choose_split(mvs_ctx *ctx, SweepParams &p, int tiles, int wgs_per_cu, const SweepFlags &f, int max_cps = INT_MAX)
 {
     const int nch = p.chunk1 - p.chunk0;
@@ -294,14 +288,25 @@ inline auto with_outputs(bool vol, bool fused, F &&f)
     return f(std::false_type{}, std::true_type{});
 }
 
+// host: calls f(std::integral_constant<int, CS>) for the cell layout of the context's sampler, so that a launch names its kernel once
+template <class F>
+inline auto with_cells(const mvs_ctx *ctx, F &&f)
+{
+    if (ctx->sampler == MVS_SAMPLER_FIXED) return f(std::integral_constant<int, CS_FIXED>{});
+    return f(std::integral_constant<int, CS_EXACT>{});
+}
+
 // the launchers: `p` carries the view / plane / row ranges; each chooses its plane split; the caller merges the partial bests
-// (merge_split_bests in sweep.hip)
+// (merge_split_bests)
 int sweep_fx_plan_general(mvs_ctx *ctx);                                    // sweep_fx.hip: the fixed-point sampler (contract v2)
 int sweep_fx_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f);
 int sweep_rect_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f);   // sweep_rect.hip: the fixed sampler on rectified views
 int sweep_xrect_plan(mvs_ctx *ctx);                                         // sweep_xrect.hip: the exact sampler on rectified views
 int sweep_xrect_launch(mvs_ctx *ctx, SweepParams &p, const SweepFlags &f);
 int warp_by_depth_fx_launch(mvs_ctx *ctx, const float *depth_dev, const float *q_dev, const uint8_t *pad_dev, int pitch, uint8_t *out2_dev);
+// select.hip: the merge of the partial bests choose_split's splits left in p.part, over the launch's rows; n packed cells as mean costs
+int merge_split_bests(mvs_ctx *ctx, const SweepParams &p);
+int unpack_volume_launch(mvs_ctx *ctx, const uint32_t *vol, float *out, size_t n);
 
 
 // Planner counters: every thread of a launch used to hit the same two or three addresses with an atomic (0.2-0.3 ms of serialised L2

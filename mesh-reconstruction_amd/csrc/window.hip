@@ -13,10 +13,9 @@
 //                        the 8 pixels add 2R + 1 row sums.  Both give the same bytes where they overlap (tests).
 //                        floor(S n / N) is a float estimate corrected by exact 32-bit integer arithmetic (window_quotient).
 //                        With `select` the kernel keeps, per pixel, the running best cell of Wv with its plane and the cells of Wv next
-//                        to it while it walks the planes, and writes the depth / cost / index maps (and the parabola of refine_depth,
-//                        sweep.hip) at the end: what mvs_sweep_argmin + mvs_sweep_refine_depth give on Wv, without reading Wv again.
-//   reader_volume        the one place that decides which packed volume argmin / refine / aggregate / clean read
-//                        (mvs_sweep_set_volume_source).
+//                        to it while it walks the planes, and writes the depth / cost / index maps (and the parabola of
+//                        select_rules.hpp) at the end: what mvs_sweep_argmin + mvs_sweep_refine_depth give on Wv, without reading Wv again.
+// Which packed volume the readers read (mvs_sweep_set_volume_source) is select.hip's decision.
 // No atomics, no scalar memory writes.
 #include "sweep_shared.hpp"
 
@@ -239,54 +238,27 @@ __global__ __launch_bounds__(64) void window_kernel(const WindowArgs a)
             }
             a.cost[p] = cell_cost<CS>(best[i] & M, best[i] >> CS);
             float zr = a.z[b];
-            if (a.refine && b > 0 && b < D - 1) {
-                const uint32_t ca_ = before[i], cb_ = best[i], cc_ = after[i];
-                if ((ca_ >> CS) != 0u && (cc_ >> CS) != 0u) {
-                    // refine_depth (sweep.hip): same operations, same order
-                    const float ca = (float)(ca_ & M) / (float)(ca_ >> CS), cb = (float)(cb_ & M) / (float)(cb_ >> CS), cc = (float)(cc_ & M) / (float)(cc_ >> CS);
-                    const float den = (ca - 2.0f * cb) + cc;
-                    if (den > 0.0f) {
-                        float t = (0.5f * (ca - cc)) / den;
-                        t = t < -0.5f ? -0.5f : (t > 0.5f ? 0.5f : t);
-                        zr = t >= 0.0f ? __builtin_fmaf(t, a.z[b + 1] - a.z[b], a.z[b]) : __builtin_fmaf(-t, a.z[b - 1] - a.z[b], a.z[b]);
-                    }
-                }
-            }
+            if (a.refine && b > 0 && b < D - 1 && (before[i] >> CS) != 0u && (after[i] >> CS) != 0u)
+                zr = refine_parabola(cell_mean<CS>(before[i]), cell_mean<CS>(best[i]), cell_mean<CS>(after[i]), a.z, b, D);
             a.depth[p] = zr;
         }
     }
 }
 
-template <int CS, bool GATED>
-void launch_window(mvs_ctx *ctx, int radius, const WindowArgs &a)
+template <int R>
+void launch_window(mvs_ctx *ctx, bool gated, const WindowArgs &a)
 {
     const dim3 grid((unsigned)div_up(a.W, kWinTileW), (unsigned)div_up(a.H, kWinTileH));
-    switch (radius) {
-    case 1: window_kernel<1, CS, GATED><<<grid, 64, 0, ctx->stream>>>(a); break;
-    case 2: window_kernel<2, CS, GATED><<<grid, 64, 0, ctx->stream>>>(a); break;
-    case 3: window_kernel<3, CS, GATED><<<grid, 64, 0, ctx->stream>>>(a); break;
-    default: window_kernel<4, CS, GATED><<<grid, 64, 0, ctx->stream>>>(a); break;
-    }
+    with_cells(ctx, [&](auto cs) {
+        constexpr int CS = decltype(cs)::value;
+        if (gated)
+            window_kernel<R, CS, (R > 0)><<<grid, 64, 0, ctx->stream>>>(a);   // radius 0 has no neighbours to gate: no such instantiation
+        else
+            window_kernel<R, CS, false><<<grid, 64, 0, ctx->stream>>>(a);
+    });
 }
 
 }  // namespace
-
-int reader_volume(mvs_ctx *ctx, const char *who, const uint32_t *&vol, size_t &bytes)
-{
-    if (ctx->volume_source != MVS_VOLUME_WINDOWED) {
-        vol = ctx->volume;
-        bytes = ctx->volume_bytes;
-        return MVS_OK;
-    }
-    vol = nullptr;
-    bytes = 0;
-    if (!ctx->have_planes || !ctx->win_planes || ctx->win_planes != ctx->D)
-        return fail(ctx, MVS_ESTATE, "%s: the volume source is MVS_VOLUME_WINDOWED and there is no windowed volume of the current %d planes (mvs_sweep_window first)", who,
-                    ctx->D);
-    vol = (const uint32_t *)ctx->win_vol.ptr;
-    bytes = (size_t)ctx->win_planes * ctx->W * ctx->H * sizeof(uint32_t);
-    return MVS_OK;
-}
 
 }  // namespace mvs
 
@@ -312,11 +284,7 @@ int mvs_sweep_window(mvs_ctx *ctx, int radius, int tau, const void *guide_dev, u
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const bool select = (flags & MVS_WINDOW_SELECT) != 0;
     int rc;
-    if (select) {
-        if ((rc = ensure(ctx, ctx->depth, P * sizeof(float)))) return rc;
-        if ((rc = ensure(ctx, ctx->cost, P * sizeof(float)))) return rc;
-        if ((rc = ensure(ctx, ctx->index, P * sizeof(int)))) return rc;
-    }
+    if (select && (rc = ensure_maps(ctx))) return rc;
     if (ctx->win_vol.bytes < N * sizeof(uint32_t)) {
         // a larger Wv: the new buffer first, so that a failed allocation leaves the old Wv as it was (ensure() frees before it allocates)
         DevBuf larger;
@@ -346,22 +314,13 @@ int mvs_sweep_window(mvs_ctx *ctx, int radius, int tau, const void *guide_dev, u
     a.tau = tau;
     a.select = select ? 1 : 0;
     a.refine = (flags & MVS_WINDOW_REFINE) ? 1 : 0;
-    const bool fx = ctx->sampler == MVS_SAMPLER_FIXED;
-    const dim3 grid((unsigned)div_up(W, kWinTileW), (unsigned)div_up(H, kWinTileH));
     ProfileScope ps(ctx, MVS_K_ARGMIN);
-    if (radius == 0) {
-        if (fx)
-            window_kernel<0, CS_FIXED, false><<<grid, 64, 0, ctx->stream>>>(a);
-        else
-            window_kernel<0, CS_EXACT, false><<<grid, 64, 0, ctx->stream>>>(a);
-    } else if (fx && gated) {
-        launch_window<CS_FIXED, true>(ctx, radius, a);
-    } else if (fx) {
-        launch_window<CS_FIXED, false>(ctx, radius, a);
-    } else if (gated) {
-        launch_window<CS_EXACT, true>(ctx, radius, a);
-    } else {
-        launch_window<CS_EXACT, false>(ctx, radius, a);
+    switch (radius) {
+    case 0: launch_window<0>(ctx, gated, a); break;
+    case 1: launch_window<1>(ctx, gated, a); break;
+    case 2: launch_window<2>(ctx, gated, a); break;
+    case 3: launch_window<3>(ctx, gated, a); break;
+    default: launch_window<4>(ctx, gated, a); break;
     }
     MVS_HIP(ctx, hipGetLastError());
     ctx->win_planes = D;
@@ -389,12 +348,3 @@ int mvs_sweep_window_fetch(mvs_ctx *ctx, uint32_t *cells_dhw)
     return MVS_OK;
 }
 
-int mvs_sweep_set_volume_source(mvs_ctx *ctx, int source)
-{
-    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_sweep_set_volume_source: null context");
-    if (source != MVS_VOLUME_RAW && source != MVS_VOLUME_WINDOWED) return fail(ctx, MVS_EINVAL, "mvs_sweep_set_volume_source: unknown source %d", source);
-    ctx->volume_source = source;
-    return MVS_OK;
-}
-
-int mvs_sweep_volume_source(const mvs_ctx *ctx) { return ctx ? ctx->volume_source : MVS_EINVAL; }

@@ -192,19 +192,10 @@ int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius,
 {
     if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_sweep_run_zncc: null context");
     if (radius < 1 || radius > 4) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_zncc: radius %d outside 1..4", radius);
-    if (flags & ~(MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN))
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_run_zncc: unknown flag bits 0x%x (MVS_SWEEP_VOLUME and MVS_SWEEP_FUSED_ARGMIN only)",
-                    flags & ~(MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN));
-    const bool vol = (flags & MVS_SWEEP_VOLUME) != 0, fused = (flags & MVS_SWEEP_FUSED_ARGMIN) != 0;
-    if (!vol && !fused) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_zncc: flags select neither volume nor fused argmin");
-    if (!ctx->have_main || !ctx->have_views || !ctx->have_planes) return fail(ctx, MVS_ESTATE, "mvs_sweep_run_zncc: set main view, side views and planes first");
-    if (ctx->sampler != MVS_SAMPLER_FIXED) return fail(ctx, MVS_ESTATE, "mvs_sweep_run_zncc: implemented for MVS_SAMPLER_FIXED (the library default)");
-    if (view_first < 0 || view_count < 0 || view_first + view_count > ctx->V)
-        return fail(ctx, MVS_EINVAL, "mvs_sweep_run_zncc: view range [%d,%d) outside 0..%d", view_first, view_first + view_count, ctx->V);
-    if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_zncc: the fixed sampler's cells hold at most 255 views (have %d)", ctx->V);
-    if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_zncc: the fixed sampler addresses images of up to 16383 x 16383");
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    bool vol, fused;
     int rc;
+    if ((rc = fx_sweep_preconditions(ctx, "mvs_sweep_run_zncc", view_first, view_count, flags, vol, fused))) return rc;
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = sweep_outputs(ctx, vol, "mvs_sweep_run_zncc"))) return rc;
     if ((rc = ensure_fx_lut(ctx))) return rc;
     SweepParams p;
@@ -219,12 +210,7 @@ int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius,
         }
     }
     MVS_HIP(ctx, hipGetLastError());
-    ctx->band_planes = 0;   // an ordinary sweep: the volume and the maps stop being a band run's (as sweep.hip: sweep_run_impl)
-    if (fused) {
-        note_full_selection(ctx);
-    } else {   // the index map is no selection on this volume: refinement and cleaning wait for one (mvs_sweep_argmin, ...)
-        ctx->sel_planes = 0;
-        ctx->sel_band_planes = 0;
-    }
+    note_ordinary_sweep(ctx);
+    fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }

@@ -1,4 +1,4 @@
-"""Crafted packed cost volumes for the depth selection and the sub-plane refinement (csrc/sweep.hip: argmin_volume, combine_best,
+"""Crafted packed cost volumes for the depth selection and the sub-plane refinement (csrc/select.hip: argmin_volume, combine_best,
 refine_depth), numpy only, and the table of cases that tests/test_select_edges_gpu.py hands to the kernels.  tests/test_select_cpu.py
 checks with the mirror alone (tests/select_mirror.py) that every generator reaches what it is here for.
 

@@ -1,8 +1,9 @@
-"""The depth selection and the sub-plane refinement on crafted volumes at the edges of their kernels (csrc/sweep.hip: argmin_volume in its
+"""The depth selection and the sub-plane refinement on crafted volumes at the edges of their kernels (csrc/select.hip: argmin_volume in its
 four instantiations and its partial form, combine_best, refine_depth): the volumes of tests/select_volumes.py go in through
 mvs_sweep_use_volume + mvs_sweep_set_planes, no sweep runs, and the maps and the 8-byte records are compared bit for bit with the numpy
 mirror (tests/select_mirror.py).  tests/test_select_cpu.py shows without a GPU what every volume is for.  The contract tests at the end
-cover what mvs_sweep_refine_depth and mvs_sweep_clean refuse; every refused call there would stay inside its buffers if it ran."""
+cover what mvs_sweep_refine_depth, mvs_sweep_clean and the entries that take a caller's volume refuse; every refused call there would stay
+inside its buffers if it ran."""
 import numpy as np
 import pytest
 import torch
@@ -212,6 +213,9 @@ def _refused(ctx, call, code, *words):
 
 
 def test_refine_refuses_a_short_volume(oracle):
+    """... and so do the entries that make the caller's volume the one of the current planes: mvs_sweep_argmin, mvs_sweep_volume_device and
+    mvs_sweep_run with MVS_SWEEP_VOLUME"""
+    from mvs_amd import synth
     case = next(c for c in sv.cases_of("parabolas") if c.sampler == "fixed" and (c.W, c.D) == (132, 17))
     vol, _ = sv.volume(case)
     cs, z = 24, oracle.plane_table(case.D, *case.z_range)
@@ -227,6 +231,25 @@ def test_refine_refuses_a_short_volume(oracle):
         ctx.sweep_use_volume(view.data_ptr(), N * 4)       # exactly enough
         ctx.sweep_refine_depth()
         _same(_maps(ctx), (want[0], want[1], mirror.refine(vol, cs, z, want[0])), "refine on a volume of exactly D H W cells")
+        short = (b"caller volume", b"%d bytes" % ((N - 1) * 4), b"need %d" % (N * 4))
+        ctx.sweep_use_volume(view.data_ptr(), (N - 1) * 4)
+        _refused(ctx, lambda: lib.mvs_sweep_argmin(ctx.h), EINVAL, *short)
+        _refused(ctx, lambda: lib.mvs_sweep_volume_device(ctx.h, None), None, *short)      # a null pointer
+        ctx.sweep_use_volume(view.data_ptr(), N * 4)
+        assert ctx.sweep_volume_device() == (view.data_ptr(), N * 4)
+        ctx.sweep_argmin()
+        _same(_maps(ctx), want, "argmin on a volume of exactly D H W cells")
+        assert _untouched(view, vol)
+        # a sweep of two views into the caller's volume
+        main_cam, main_img, side_cams, sides = synth.make_views(case.W, case.H, 2, radius=0.3)[:4]
+        ctx.sweep_set(main_cam, main_img, side_cams, sides, case.D)
+        ctx.sweep_use_volume(view.data_ptr(), (N - 1) * 4)
+        _refused(ctx, lambda: lib.mvs_sweep_run(ctx.h, 0, 2, mvs_amd.MVS_SWEEP_VOLUME), EINVAL, *short)
+        assert _untouched(view, vol)
+        ctx.sweep_use_volume(view.data_ptr(), N * 4)
+        ctx.sweep_run(0, 2, mvs_amd.MVS_SWEEP_VOLUME)
+        swept = ctx.sweep_fetch(want_volume=True)[3]
+        assert not _untouched(view, vol) and _untouched(view, swept), "the sweep wrote the caller's volume of exactly D H W cells"
 
 
 def test_a_selection_over_other_planes_is_refused(oracle):
