@@ -382,6 +382,39 @@ int mvs_sweep_band_report(mvs_ctx *ctx, int out[4]);
  * (MVS_SWEEP_FORCE_GENERIC and MVS_SWEEP_NO_RECT are unknown here), a caller's volume that is too small; MVS_ESTATE without main view,
  * views or planes, for the exact sampler; MVS_ENOMEM.  After an error nothing is written and the context stays usable. */
 int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius, unsigned flags);
+/* Occlusion-robust sweep: the cell keeps the K best views (csrc/bestk.hip; DESIGN.md section 22 is the contract; integers throughout
+ * except rule 4 of the ZNCC cost; bit-identical to tests/bestk_mirror.py).  Fixed sampler only.  Every other sweep merges the side views
+ * of a cell by summing their costs, so a view in which a nearer surface hides the point adds a wrong cost; next to a depth step the sum
+ * then picks the wrong plane.  This one merges only the `keep` lowest per-view costs of the cell (Kang and Szeliski's best-half rule).
+ * The planes are the context's plane table, the views [view_first, view_first + view_count).
+ *   1. Per-view cost of (pixel p, plane d, view v), a flag `counted` and an integer c:
+ *      MVS_COST_ZNCC, radius 1..4: counted and c (0..65024) exactly as rules 1-4 of mvs_sweep_run_zncc.
+ *      MVS_COST_ABSDIFF, radius 0..4: e(q) = |dot(q) - 255 A(q)| and ok(q) are mvs_sweep_run's own sample at every pixel q, bit for bit.
+ *      The members M are the pixels q of the frame with |q.row - p.row| <= radius, |q.col - p.col| <= radius and ok(q); pixels outside
+ *      the frame are no members.  The view is counted iff ok(p).  N = |M|, S = the sum of e over M (at most 81 * 65025, below 2^23),
+ *      c = S / N in integer division, 0..65025; no float is used anywhere.  At radius 0, c = e(p).
+ *   2. Cell: n = the number of counted views of the range, k = min(keep, n); the cell is k << 24 | (the sum of the k smallest c), and 0
+ *      if n = 0.  The sum of the k smallest values does not depend on how equal values are ordered: there is no tie rule.  keep is 1..8,
+ *      or MVS_KEEP_ALL (0) for every counted view: with MVS_COST_ZNCC that is mvs_sweep_run_zncc's volume, with MVS_COST_ABSDIFF at
+ *      radius 0 mvs_sweep_run's.  Layout [D][H][W] u32 in the context's packed volume (its own or the caller's), written, not added to.
+ *   3. The cell keeps the packed format and its scale (mean cost = sum / (255 count), rule 6 of mvs_sweep_run_zncc for the ZNCC cost), so
+ *      mvs_sweep_argmin, _refine_depth, _window, _aggregate, _clean, the depth store and the TSDF run on it unchanged, and
+ *      MVS_SWEEP_FUSED_ARGMIN gives what mvs_sweep_argmin gives on that volume and records a full selection; without the flag the context
+ *      has no depth selection until a selecting call.  It ends a band run's state exactly as mvs_sweep_run does.
+ *   4. Unlike the summing sweeps, the volumes of disjoint view ranges DO NOT ADD: the k best of a range are not the k best of its parts.
+ *      mvs_comm's view-sharded modes must not be fed with it; the rows mode needs nothing.
+ * Use it with a window: the minimum over views of a single-pixel cost is mostly texture aliasing, and best-K of them is WORSE than the
+ * sum (DESIGN.md section 22 has the figures).  Radius 0 exists as a cross-check against mvs_sweep_run.
+ * It works on the staged state however it got there, is asynchronous on the context's stream and timed under MVS_K_SWEEP.  A context that
+ * never calls it allocates nothing for it.
+ * Errors: MVS_EINVAL for a NULL ctx, an unknown cost, a radius outside the cost's range (0 with MVS_COST_ZNCC is one), keep outside 0..8,
+ * a view range outside 0..V, flags that select neither output, unknown flag bits (MVS_SWEEP_FORCE_GENERIC and MVS_SWEEP_NO_RECT are
+ * unknown here), a caller's volume that is too small; MVS_ESTATE without main view, views or planes, for the exact sampler; MVS_ENOMEM.
+ * After an error nothing is written and the context stays usable. */
+#define MVS_COST_ABSDIFF 0   /* windowed |dot - 255 I_main| */
+#define MVS_COST_ZNCC    1   /* rules 1-4 of mvs_sweep_run_zncc */
+#define MVS_KEEP_ALL     0   /* keep: every counted view */
+int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, int radius, int keep, unsigned flags);
 /* Resolution pyramid: a half-resolution coarse level for the band sweep (csrc/pyramid.hip; DESIGN.md section 20 is the contract;
  * bit-identical to tests/pyramid_mirror.py).  The levels are separate contexts on the SAME GPU: `fine` is W x H with W and H even,
  * `coarse` exactly (W/2) x (H/2).  The cameras are NDC matrices and the centre of a coarse pixel is the mean of the centres of its four

@@ -117,6 +117,54 @@ __device__ __forceinline__ void store_best(const SweepParams &p, size_t pix, uin
 }
 
 
+// ------------------------------------------------------------------------------------------------------
+// the windowed sweeps' tile (zncc.hip: sweep_fx_zncc, bestk.hip: sweep_fx_bestk) and the ZNCC window element
+// ------------------------------------------------------------------------------------------------------
+constexpr int ZN_TW = 32, ZN_TH = 16;    // pixels per tile
+constexpr int ZN_THREADS = 256;          // two pixels each
+constexpr int ZN_PC = 2;                 // planes per accumulator chunk (4 and 8 spill scalar registers: DESIGN.md section 21)
+constexpr float ZN_MAGIC = 12582912.0f;  // 1.5 * 2^23, as sweep_fx.hip's FX_MAGIC
+
+template <int R>
+struct ZnShape {
+    static constexpr int HW = ZN_TW + 2 * R, HH = ZN_TH + 2 * R;               // tile + halo
+    static constexpr int SAMPLES = HW * HH, ROWSUMS = HH * ZN_TW;              // elements of the two LDS buffers
+    static constexpr int NS = (SAMPLES + ZN_THREADS - 1) / ZN_THREADS;         // samples per thread (3 or 4)
+    static constexpr int NR = (ROWSUMS + ZN_THREADS - 1) / ZN_THREADS;         // row sums per thread (3)
+};
+
+__device__ __forceinline__ uint4 add4(uint4 a, uint4 b) { return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// band.hip's sample (sweep_fx.hip: sample_global_fx) -> the window element of the position: a = A(q), aa = a a.  A position outside the
+// main frame carries NaN in its affine part, which fails the sampler's own s.w > 0 test like a sample outside the view's frame
+__device__ __forceinline__ uint4 zncc_sample(const Affine &A, float bx, float by, float bw, float z, const uint32_t *__restrict__ quads, uint32_t pitch, float hix, float hiy,
+                                             const uint32_t *__restrict__ lut, uint32_t a, uint32_t aa)
+{
+    const float sx = __builtin_fmaf(z, bx, A.ax), sy = __builtin_fmaf(z, by, A.ay), sw = __builtin_fmaf(z, bw, A.aw);
+    const float r256 = rcp_rn(sw) * 256.0f;
+    const float tx = __builtin_fmaf(sx, r256, ZN_MAGIC + 4.0f), ty = __builtin_fmaf(sy, r256, ZN_MAGIC + 4.0f);
+    const bool ok = sw > 0.0f && tx > ZN_MAGIC + 132.0f && tx < hix && ty > ZN_MAGIC + 132.0f && ty < hiy;  // false for NaN
+    const uint32_t ux = __builtin_bit_cast(uint32_t, tx) & 0x3fffffu, uy = __builtin_bit_cast(uint32_t, ty) & 0x3fffffu;  // t - magic
+    const uint32_t quad = quads[ok ? (uy >> 8) * pitch + (ux >> 8) : 0u];   // in frame: column <= W, row <= H of the (H + 2) x pitch quad image
+    const uint32_t w = lut[(((uy >> 3) & 31u) << 5) | ((ux >> 3) & 31u)];
+    const uint32_t dot = __builtin_amdgcn_udot4(quad, w, 0u, false);   // <= 65025
+    const uint32_t b = (dot + 127u) / 255u;                            // rule 1: the grey level mvs_warp_by_depth returns
+    return ok ? make_uint4(a | (b << 16), umul24u(a, b) | (1u << 24), aa, umul24u(b, b)) : make_uint4(0u, 0u, 0u, 0u);
+}
+
+// rules 3-5: the window's sums -> the view's contribution to the cell
+__device__ __forceinline__ uint32_t zncc_cell(uint4 s, uint32_t centre_ok)
+{
+    const int N = (int)(s.y >> 24), Sab = (int)(s.y & 0xffffffu), Sa = (int)(s.x & 0xffffu), Sb = (int)(s.x >> 16), Saa = (int)s.z, Sbb = (int)s.w;
+    const int cov = N * Sab - Sa * Sb, va = N * Saa - Sa * Sa, vb = N * Sbb - Sb * Sb;   // all below 2^31 (81 * 81 * 65025)
+    const bool counted = centre_ok != 0u && va > 0 && vb > 0;
+    const float den = sqrtf((float)max(va, 1) * (float)max(vb, 1));   // (the max: no 0 / 0 in a lane that is dropped anyway)
+    float ncc = (float)cov / den;
+    ncc = fminf(fmaxf(ncc, -1.0f), 1.0f);
+    const uint32_t c = (uint32_t)floorf(32512.0f * (1.0f - ncc));     // 0 .. 65024
+    return counted ? (1u << 24) + c : 0u;
+}
+
 // wave-uniform value -> SGPR
 __device__ __forceinline__ float uniform_f(float x)
 {

@@ -21,6 +21,8 @@ MVS_SWEEP_VOLUME = 1
 MVS_SWEEP_FUSED_ARGMIN = 2
 MVS_SWEEP_FORCE_GENERIC = 4
 MVS_SWEEP_NO_RECT = 8
+MVS_COST_ABSDIFF, MVS_COST_ZNCC = 0, 1
+MVS_KEEP_ALL = 0
 MVS_AGGREGATE_REFINE = 1
 MVS_CLEAN_SCORES_AGGREGATED = 1
 MVS_WINDOW_SELECT, MVS_WINDOW_REFINE = 1, 2
@@ -138,6 +140,7 @@ ABI = [
     ("mvs_sweep_band_fetch", _i, [_vp, _fp]),
     ("mvs_sweep_band_report", _i, [_vp, C.POINTER(_i)]),
     ("mvs_sweep_run_zncc", _i, [_vp, _i, _i, _i, C.c_uint]),
+    ("mvs_sweep_run_bestk", _i, [_vp, _i, _i, _i, _i, _i, C.c_uint]),
     ("mvs_pyramid_downsample_device", _i, [_vp, _vp, _vp, _i]),
     ("mvs_pyramid_stage", _i, [_vp, _vp]),
     ("mvs_pyramid_prior", _i, [_vp, _vp, _vp, _i]),
@@ -1172,6 +1175,15 @@ class Context:
         if view_count is None:
             view_count = self.V - view_first
         self._check(self.lib.mvs_sweep_run_zncc(self.h, int(view_first), int(view_count), int(radius), int(flags)))
+
+    def sweep_run_bestk(self, cost, radius=2, keep=2, view_first=0, view_count=None, flags=MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN):
+        """mvs_sweep_run_bestk: the fixed sampler's sweep whose cell keeps the `keep` lowest per-view windowed costs (1..8, or MVS_KEEP_ALL)
+        instead of the sum over every view, so that views in which the point is hidden drop out; cost MVS_COST_ZNCC (radius 1..4) or
+        MVS_COST_ABSDIFF (radius 0..4; 0 is a cross-check, best-K of single-pixel costs is worse than the sum).  The same packed volume
+        and maps as sweep_run; the volumes of disjoint view ranges do not add (asynchronous, stream-ordered)"""
+        if view_count is None:
+            view_count = self.V - view_first
+        self._check(self.lib.mvs_sweep_run_bestk(self.h, int(view_first), int(view_count), int(cost), int(radius), int(keep), int(flags)))
 
     # ---- resolution pyramid (include/mvs.h, DESIGN.md section 20) --------------------------------
     def pyramid_downsample_device(self, src_ptr, dst_ptr, nframes=1):
