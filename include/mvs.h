@@ -454,6 +454,43 @@ int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, 
 int mvs_pyramid_downsample_device(mvs_ctx *fine, const void *src_dev, void *dst_dev, int nframes);
 int mvs_pyramid_stage(mvs_ctx *fine, mvs_ctx *coarse);
 int mvs_pyramid_prior(mvs_ctx *fine, mvs_ctx *coarse, const void *coarse_depth_dev /* NULL: coarse's depth map */, int tau);
+/* Depth-map filter: a gated median and a gated mean of a selected depth map (csrc/depth_filter.hip; DESIGN.md section 23 is the contract;
+ * all f32, one rounding per operation and no contraction, bit-identical to tests/depth_filter_mirror.py).  The windowed costs assume a
+ * fronto-parallel surface inside their window, so the depth they select on a slanted surface is biased and noisy, and the band sweep's
+ * window follows its prior: a smooth prior makes it a slanted support window.  This smooths a map without crossing the edges of a guide
+ * image or of the map itself, and fills the holes mvs_sweep_clean leaves.
+ *   1. Valid: a value z of the map is valid when -1 < z < 1 (NaN, +-inf, -1 and 1 are not) and is read as z + 0.0f (-0.0 becomes +0.0).
+ *   2. Window of pixel p: every pixel q of the frame with |q.row - p.row| <= radius and |q.col - p.col| <= radius, in row-major order.
+ *      Guide gate: |G(q) - G(p)| <= tau in integers (p itself always passes; tau = 255 lets every pixel pass and G is not read).
+ *   3. Median stage (MVS_FILTER_MEDIAN): the members of p are the valid q that pass the guide gate, n their number.  A valid p gets the
+ *      lower median, the member of rank (n - 1) / 2 in ascending order.  An invalid p gets MVS_BACKGROUND_DEPTH; with MVS_FILTER_FILL and
+ *      n >= min_members it gets the lower median of its members instead.  No arithmetic: the output is one of the inputs.
+ *   4. Mean stage (MVS_FILTER_MEAN), on the median stage's output m when both flags are given, else on the input: for a valid p the
+ *      members are the valid q that pass the guide gate and the depth gate fabsf(m(q) - m(p)) <= max_step (+inf: no depth gate, 0: equal
+ *      values only); the output is (the sum of the members, added one at a time in window order starting from 0.0f) / (float)n.  An
+ *      invalid p stays MVS_BACKGROUND_DEPTH: holes are filled by the median stage only.
+ *   5. The output holds 1.0 only as background and never -1.0: a mean of values inside (-1, 1) stays inside.
+ * max_step is in depth units: a few plane steps of the sweep that selected the map.  A max_step below the surface's own change of depth
+ * across the window cuts a slanted surface into terraces and makes it worse than no filter (DESIGN.md section 23 has the figures).
+ *   depth_dev: H * W f32 on the context's GPU in the library's depth convention -- mvs_sweep_depth_device, mvs_sweep_band_depth_device,
+ * mvs_tsdf_raycast_depth_device, mvs_depth_slot_device, mvs_depth_filtered_device itself (the filtered map of an earlier call), or a band
+ * run's offset map (its values lie inside (-1, 1)).  guide_dev: H * W u8, NULL = the staged main image, exactly as in mvs_sweep_window.
+ * The filtered map is a context-owned H * W f32 map, allocated by the first call together with one intermediate map; a context that
+ * never calls the filter allocates nothing.  Asynchronous on the context's stream, timed under MVS_K_ARGMIN.  The call touches no other
+ * state: the sweep's depth / cost / index maps, the selection state, the band state and the volume source are as they were.
+ * Errors: MVS_EINVAL for a NULL ctx, depth_dev or fetch array, a radius outside 1..4, tau outside 0..255, a negative or NaN max_step,
+ * flags with neither stage or with unknown bits, MVS_FILTER_FILL without MVS_FILTER_MEDIAN, min_members outside 1..81 with
+ * MVS_FILTER_FILL (ignored without); MVS_ESTATE for tau < 255 with a NULL guide and no staged main image, and for
+ * mvs_depth_filter_fetch before the first call; MVS_ENOMEM.  After an error nothing is written and the context stays usable.
+ * mvs_depth_filtered_device: the filtered map (NULL before the first call; the address does not change afterwards);
+ * mvs_depth_filter_fetch synchronises and downloads it. */
+#define MVS_FILTER_MEDIAN 1u
+#define MVS_FILTER_MEAN 2u
+#define MVS_FILTER_FILL 4u
+int mvs_depth_filter(mvs_ctx *ctx, const void *depth_dev, const void *guide_dev /* NULL: the staged main image */, int radius, int tau, float max_step, int min_members,
+                     unsigned flags);
+void *mvs_depth_filtered_device(mvs_ctx *ctx);
+int mvs_depth_filter_fetch(mvs_ctx *ctx, float *depth_hw);
 /* The same selection in two steps, for a view-sharded job that REDUCE-SCATTERS the packed volume instead of all-reducing it
  * (half the bytes over xGMI): rank r owns the summed cells of planes [plane_first, plane_first + plane_count) in
  * `volume_slice_dev` ([plane_count][H][W] u32) and selects a partial best per pixel over them -- `partial_out_dev` receives

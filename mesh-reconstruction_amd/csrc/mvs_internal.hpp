@@ -218,6 +218,10 @@ struct mvs_ctx {
     // stream ran on the other level's buffers), created by the first pyramid call, without timing
     mvs::DevBuf pyr_frames;
     hipEvent_t pyr_events[2] = {nullptr, nullptr};
+    // depth-map filter (depth_filter.hip: mvs_depth_filter): the filtered map followed by the intermediate map of a two-stage call, H*W f32
+    // each, one allocation made by the first call; dfilter_have: a call has written the filtered map
+    mvs::DevBuf dfilter_maps;
+    bool dfilter_have = false;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

@@ -27,6 +27,7 @@ MVS_AGGREGATE_REFINE = 1
 MVS_CLEAN_SCORES_AGGREGATED = 1
 MVS_WINDOW_SELECT, MVS_WINDOW_REFINE = 1, 2
 MVS_VOLUME_RAW, MVS_VOLUME_WINDOWED = 0, 1
+MVS_FILTER_MEDIAN, MVS_FILTER_MEAN, MVS_FILTER_FILL = 1, 2, 4
 VOLUME_SOURCES = {"raw": MVS_VOLUME_RAW, "windowed": MVS_VOLUME_WINDOWED}
 MVS_SHARD_ROWS, MVS_SHARD_VIEWS, MVS_SHARD_VIEWS_SCATTER = 0, 1, 2
 SHARD_MODES = {"rows": 0, "views": 1, "views_scatter": 2}
@@ -144,6 +145,9 @@ ABI = [
     ("mvs_pyramid_downsample_device", _i, [_vp, _vp, _vp, _i]),
     ("mvs_pyramid_stage", _i, [_vp, _vp]),
     ("mvs_pyramid_prior", _i, [_vp, _vp, _vp, _i]),
+    ("mvs_depth_filter", _i, [_vp, _vp, _vp, _i, _i, _f, _i, C.c_uint]),
+    ("mvs_depth_filtered_device", _vp, [_vp]),
+    ("mvs_depth_filter_fetch", _i, [_vp, _fp]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
     ("mvs_sweep_combine_partials", _i, [_vp, _vp, _i]),
     ("mvs_sweep_volume_device", _vp, [_vp, C.POINTER(_sz)]),
@@ -425,32 +429,57 @@ def pinned_array(shape, dtype):
     return arr
 
 
-def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, fetch=True):
+def _filter_step(ctx, depth_ptr, filter, step, fetch=False):
+    """the `filter` keyword of the coarse-to-fine helpers: median then mean of the map at depth_ptr, the depth gate max_steps plane steps
+    of the level that selected it -> the device address of the filtered map (fetch: the map itself)"""
+    unknown = set(filter) - {"radius", "tau", "max_steps"}
+    if unknown:
+        raise ValueError("filter: unknown keys %s (radius, tau, max_steps)" % sorted(unknown))
+    out = ctx.depth_filter(depth_ptr, radius=filter.get("radius", 4), tau=filter.get("tau", 255),
+                           max_step=float(np.float32(float(filter.get("max_steps", float("inf"))) * step)), fetch=fetch)
+    return out if fetch else ctx.depth_filtered_pointer()
+
+
+def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, fetch=True, filter=None):
     """Two-level sweep on the inputs staged on `ctx` (main view and side views; fixed sampler): `coarse_planes` planes over [z_lo, z_hi],
     refined; then `band_planes` planes within +- band_steps coarse steps of that map (mvs_sweep_run_band with the context's own depth map
     as the prior), refined and resolved.  Pure composition of Context calls -> the absolute depth map (H, W) float32 (fetch=False: None,
     the map stays on the device: sweep_band_pointers()[0]); the context is left
     with the band's plane table, volume and maps (the depth map holds offsets), and sweep_band_report() tells how the band fared.  A wrong
-    coarse depth confines the band to the wrong place: this lowers the median error, not the outliers."""
+    coarse depth confines the band to the wrong place: this lowers the median error, not the outliers.
+    filter: None, or dict(radius=, tau=, max_steps=): the coarse map is filtered (Context.depth_filter, median then mean, the guide the
+    staged main image) before it becomes the band's prior, and so is the resolved map; the depth gate is max_steps plane steps of the
+    level that selected the map.  The filtered resolved map is returned (fetch=False: it stays at depth_filtered_pointer())."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     ctx.sweep_set_planes(coarse_planes, z_lo, z_hi)
     ctx.sweep_run(0, None, flags)
     ctx.sweep_refine_depth()
+    prior = ctx.sweep_result_pointers()[0]
+    if filter is not None:
+        prior = _filter_step(ctx, prior, filter, (float(z_hi) - float(z_lo)) / coarse_planes)
     hb = float(np.float32(band_steps * (float(z_hi) - float(z_lo)) / coarse_planes))
     ctx.sweep_set_planes(band_planes, -hb, hb)
-    ctx.sweep_run_band(ctx.sweep_result_pointers()[0], 0, None, flags)
+    ctx.sweep_run_band(prior, 0, None, flags)
     ctx.sweep_refine_depth()
-    return ctx.sweep_band_resolve(fetch=fetch)
+    if filter is None:
+        return ctx.sweep_band_resolve(fetch=fetch)
+    ctx.sweep_band_resolve(fetch=False)
+    out = _filter_step(ctx, ctx.sweep_band_pointers()[0], filter, 2.0 * hb / band_planes, fetch=fetch)
+    return out if fetch else None
 
 
-def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, tau=255, fetch=True):
+def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, tau=255, fetch=True, filter=None):
     """Coarse-to-fine over a resolution pyramid: ctxs = [fine, half] or [fine, half, quarter], each level a context
     of exactly half the size of the one before it, on one GPU, with the inputs staged on ctxs[0].  Stages down the chain (pyramid_stage);
     coarsest level: `coarse_planes` planes over [z_lo, z_hi], refined; each finer level: its prior from the level below (pyramid_prior with
     `tau`), then `band_planes` planes within +- band_steps plane steps of the level below (a band level's step is its band width over
     band_planes), refined and resolved.  Pure composition of Context calls, like coarse_to_fine -> the finest level's absolute depth map
     (H, W) float32 (fetch=False: None, the map stays on the device: ctxs[0].sweep_band_pointers()[0]); every level is left with its own
-    plane table, volume and maps."""
+    plane table, volume and maps.
+    filter: None, or dict(radius=, tau=, max_steps=): each level's upsampled prior is filtered on that level (Context.depth_filter, median
+    then mean, the guide the level's staged main image) before its band run, and so is the finest level's resolved map, which is then what
+    is returned (fetch=False: it stays at ctxs[0].depth_filtered_pointer()); the depth gate is max_steps plane steps of the level that
+    selected the map."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     for above, below in zip(ctxs, ctxs[1:]):
         above.pyramid_stage(below)
@@ -462,13 +491,19 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
     for level in range(len(ctxs) - 2, -1, -1):
         ctx = ctxs[level]
         ctx.pyramid_prior(ctxs[level + 1], depth_ptr, tau)
+        prior = ctx.sweep_band_pointers()[1]
+        if filter is not None:
+            prior = _filter_step(ctx, prior, filter, step)
         hb = float(np.float32(band_steps * step))
         ctx.sweep_set_planes(band_planes, -hb, hb)
-        ctx.sweep_run_band(ctx.sweep_band_pointers()[1], 0, None, flags)
+        ctx.sweep_run_band(prior, 0, None, flags)
         ctx.sweep_refine_depth()
-        out = ctx.sweep_band_resolve(fetch=fetch and level == 0)
+        out = ctx.sweep_band_resolve(fetch=fetch and level == 0 and filter is None)
         depth_ptr = ctx.sweep_band_pointers()[0]
         step = 2.0 * hb / band_planes
+    if filter is not None and len(ctxs) > 1:
+        out = _filter_step(ctxs[0], depth_ptr, filter, step, fetch=fetch)
+        out = out if fetch else None
     return out
 
 
@@ -1184,6 +1219,29 @@ class Context:
         if view_count is None:
             view_count = self.V - view_first
         self._check(self.lib.mvs_sweep_run_bestk(self.h, int(view_first), int(view_count), int(cost), int(radius), int(keep), int(flags)))
+
+    # ---- depth-map filter (include/mvs.h) -----------------------------------
+    def depth_filter(self, depth_ptr, radius=4, tau=255, max_step=float("inf"), guide_ptr=None, median=True, mean=True, fill=0, fetch=True):
+        """mvs_depth_filter: the gated median (`median`) and / or gated mean (`mean`) over the (2 radius + 1)^2 window of the H*W float32
+        depth map at device address depth_ptr (sweep_result_pointers()[0], sweep_band_pointers()[0], tsdf_raycast_pointers()[0],
+        depth_slot_pointer(slot), depth_filtered_pointer(), ...).  A neighbour counts when its guide value is within `tau` of the
+        pixel's (guide_ptr: H*W uint8, None = the staged main image; tau 255 = no guide) and, in the mean, when its depth is within
+        max_step of the pixel's (inf = no depth gate).  fill = k > 0: the median also fills an invalid pixel that has at least k valid
+        members.  max_step is in depth units, a few plane steps: below the surface's own change of depth across the window it makes a
+        slanted surface worse.  fetch: -> (H, W) float32 (synchronises), else None (asynchronous, stream-ordered; the map stays at
+        depth_filtered_pointer())"""
+        flags = (MVS_FILTER_MEDIAN if median else 0) | (MVS_FILTER_MEAN if mean else 0) | (MVS_FILTER_FILL if fill else 0)
+        self._check(self.lib.mvs_depth_filter(self.h, C.c_void_p(int(depth_ptr)) if depth_ptr else None, C.c_void_p(int(guide_ptr)) if guide_ptr else None,
+                                              int(radius), int(tau), float(max_step), int(fill), flags))
+        if not fetch:
+            return None
+        depth = np.empty((self.H, self.W), np.float32)
+        self._check(self.lib.mvs_depth_filter_fetch(self.h, _ptr(depth, _fp)))
+        return depth
+
+    def depth_filtered_pointer(self):
+        """device address of the filtered map of the last depth_filter (0 before the first)"""
+        return self.lib.mvs_depth_filtered_device(self.h) or 0
 
     # ---- resolution pyramid (include/mvs.h, DESIGN.md section 20) --------------------------------
     def pyramid_downsample_device(self, src_ptr, dst_ptr, nframes=1):
