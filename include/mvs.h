@@ -415,6 +415,37 @@ int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius,
 #define MVS_COST_ZNCC    1   /* rules 1-4 of mvs_sweep_run_zncc */
 #define MVS_KEEP_ALL     0   /* keep: every counted view */
 int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, int radius, int keep, unsigned flags);
+/* Band sweep with windowed costs: mvs_sweep_run_bestk with plane d of pixel q at prior(q) + delta_d (csrc/band_bestk.hip; DESIGN.md
+ * section 24 is the contract; bit-identical to tests/band_bestk_mirror.py).  Fixed sampler only.  It joins the band sweep's planes, spent
+ * where a prior says the surface is, with the matching costs that survive exposure drift (ZNCC) and occlusion (best-K), so that the
+ * coarse-to-fine paths can run on frames on which the absolute difference fails.  MVS_COST_ZNCC with MVS_KEEP_ALL is the ZNCC band sweep.
+ *   1. Prior and planes: rules 1-2 of mvs_sweep_run_band.  A pixel q has a prior when -1 < prior(q) < 1; z_d(q) = prior(q) + delta_d is one
+ *      f32 add, delta the context's plane table inside (-1, 1); plane d is live at q when q has a prior and -1 < z_d(q) < 1.
+ *   2. Sample: ok(q) and dot(q) of (q, d, v) are the fixed sampler's sample of mvs_sweep_run, bit for bit, at (xn(q), yn(q), z_d(q)).  A q
+ *      outside the frame, without a prior or on a dead plane is not ok.  EVERY WINDOW MEMBER IS SAMPLED AT ITS OWN PRIOR: the window
+ *      follows the prior surface, a slanted support window where the prior is smooth.
+ *   3. Per-view cost of (p, d, v): rule 1 of mvs_sweep_run_bestk on those samples -- the ZNCC cost (rules 1-4 of mvs_sweep_run_zncc,
+ *      B(q) = (dot(q) + 127) / 255; radius 1..4) or the integer mean of |dot(q) - 255 A(q)| over the members (radius 0..4).  The members
+ *      are the q of the window with ok(q); the view counts iff ok(p), and for ZNCC also va > 0 and vb > 0.
+ *   4. Cell: rule 2 of mvs_sweep_run_bestk, k << 24 | (the sum of the k smallest c), keep 1..8 or MVS_KEEP_ALL; layout [D][H][W] u32 in the
+ *      context's packed volume (its own or the caller's), written, not added to.  The volumes of disjoint view ranges add only with
+ *      MVS_KEEP_ALL.
+ *   5. Selection and state: rules 4-5 of mvs_sweep_run_band unchanged.  MVS_SWEEP_FUSED_ARGMIN gives what mvs_sweep_argmin gives on that
+ *      volume; THE DEPTH MAP HOLDS OFFSETS.  The call copies the prior into the context's prior buffer, so prior_dev may be
+ *      mvs_sweep_depth_device(ctx), mvs_sweep_band_prior_device(ctx) (no copy) or mvs_depth_filtered_device(ctx).  It leaves the band
+ *      state exactly as mvs_sweep_run_band does: mvs_sweep_band_resolve / _report / _fetch, mvs_sweep_argmin, _refine_depth, _window,
+ *      _aggregate, _clean and mvs_pyramid_prior work on it unchanged, and an ordinary sweep ends it.
+ * Three identities hold bit for bit: with prior == 0.0 everywhere the volume is mvs_sweep_run_bestk's on the same table; MVS_COST_ABSDIFF
+ * at radius 0 with MVS_KEEP_ALL gives mvs_sweep_run_band's volume; MVS_COST_ZNCC with MVS_KEEP_ALL and prior == 0.0 gives
+ * mvs_sweep_run_zncc's.
+ * A wrong prior confines the band to the wrong place, and a windowed cost makes that worse, not better: on a RAW coarse map the windowed
+ * band is worse than the global windowed sweep at equal samples; filter the prior first (mvs_depth_filter; DESIGN.md section 24 has the
+ * figures).  Asynchronous on the context's stream, timed under MVS_K_SWEEP.  A context that never calls it allocates nothing for it.
+ * Errors: MVS_EINVAL for a NULL ctx or prior, an unknown cost, a radius outside the cost's range, keep outside 0..8, a view range outside
+ * 0..V, flags that select neither output, unknown flag bits, a caller's volume that is too small; MVS_ESTATE without main view, views or
+ * planes, for a plane table not inside (-1, 1), for the exact sampler; MVS_ENOMEM.  After an error nothing is written and the context
+ * stays usable. */
+int mvs_sweep_run_band_bestk(mvs_ctx *ctx, int view_first, int view_count, const void *prior_dev, int cost, int radius, int keep, unsigned flags);
 /* Resolution pyramid: a half-resolution coarse level for the band sweep (csrc/pyramid.hip; DESIGN.md section 20 is the contract;
  * bit-identical to tests/pyramid_mirror.py).  The levels are separate contexts on the SAME GPU: `fine` is W x H with W and H even,
  * `coarse` exactly (W/2) x (H/2).  The cameras are NDC matrices and the centre of a coarse pixel is the mean of the centres of its four

@@ -1,0 +1,229 @@
+// band_bestk.hip -- band sweep with windowed costs: the occlusion-robust sweep's cell (bestk.hip) on the band sweep's planes (band.hip)
+// (DESIGN.md section 24 is the contract; tests/band_bestk_mirror.py states it with integer arrays).
+//
+// Plane d of pixel q is  z_d(q) = prior(q) + delta_d  with delta the context's plane table.  The per-view cost of (p, d, v) is section
+// 22's windowed cost -- ZNCC, or the integer mean of |dot - 255 I_main| -- over samples each taken at ITS OWN pixel's plane: window member
+// q is sampled at z_d(q), not at z_d(p), so the window follows the prior surface (a slanted support window where the prior is smooth).
+// The cell is k << 24 | the sum of the k smallest per-view costs; MVS_COST_ZNCC with MVS_KEEP_ALL is the ZNCC band sweep.  The volume is
+// the packed volume and the state the band state, so everything behind either runs unchanged.
+//
+// sweep_fx_band_bestk<COST, R, KMAX> is sweep_fx_bestk with one difference: each of the thread's sample positions loads its prior once, and
+// the z of a sample is prior + delta_d, or NaN for a dead plane (no prior, or the sum outside (-1, 1)); the sampler's own s.w > 0 test
+// rejects NaN, as in band.hip, so there is no second mask.  A position outside the frame carries NaN already.  The add and the range test
+// are done per (view, plane, sample), not once per chunk: a chunk's planes kept in NS x ZN_PC registers cost a wave per SIMD in most
+// instantiations and, where they did, 7 % at 1080p x 16 views.  The same 36 instantiations; tile, LDS, window
+// sums and merge are bestk.hip's (bestk_rules.hpp).
+#include "bestk_rules.hpp"
+
+namespace mvs {
+
+int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the 32 x 32 weight table on the device
+
+namespace {
+
+template <int COST, int R, int KMAX>
+__global__ __launch_bounds__(ZN_THREADS) void sweep_fx_band_bestk(SweepParams p, const uint32_t *__restrict__ lut_g, const float *__restrict__ prior, int keep, int write_volume,
+                                                                   int fused)
+{
+    using S = ZnShape<R>;
+    using C = BkCost<COST>;
+    using Elem = typename C::Elem;
+    constexpr bool ZNCC = COST == MVS_COST_ZNCC;
+    constexpr bool WINDOW = R > 0;
+    __shared__ uint32_t lut[1024];
+    __shared__ Elem smp[WINDOW ? S::SAMPLES : 1];    // [HH][HW] window elements of the current (plane, view)
+    __shared__ Elem rows[WINDOW ? S::ROWSUMS : 1];   // [HH][32] horizontal sums
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 4; i++) lut[tid + ZN_THREADS * i] = lut_g[tid + ZN_THREADS * i];
+    __syncthreads();
+    const int x0 = blockIdx.x * ZN_TW, y0 = blockIdx.y * ZN_TH;
+    // this thread's sample positions: elements tid + 256 s of tile + halo (R = 0: its own two pixels), each with its own prior
+    float sxn[S::NS], syn[S::NS], sz0[S::NS];
+    uint32_t sa[S::NS], saa[S::NS];   // ZNCC: a, a a; absolute difference: 255 a, unused
+#pragma unroll
+    for (int s = 0; s < S::NS; s++) {
+        const int i = tid + ZN_THREADS * s;
+        const int hy = i / S::HW, hx = i - hy * S::HW;
+        const int col = x0 - R + hx, row = y0 - R + hy;
+        const bool live = i < S::SAMPLES && col >= 0 && col < p.W && row >= 0 && row < p.H;   // pixels outside the frame are no members
+        const size_t at = live ? (size_t)row * p.W + col : 0;
+        const uint32_t a = live ? (uint32_t)p.main_img[at] : 0u;
+        const float z0 = prior[at];
+        sa[s] = ZNCC ? a : 255u * a;
+        saa[s] = a * a;
+        sxn[s] = live ? __builtin_fmaf((float)(2 * col + 1), p.invW, -1.0f) : __builtin_nanf("");
+        syn[s] = __builtin_fmaf(-(float)(2 * row + 1), p.invH, 1.0f);
+        sz0[s] = (live && z0 > -1.0f && z0 < 1.0f) ? z0 : __builtin_nanf("");   // section 19 rule 1 (false for NaN)
+    }
+    const int c = tid & (ZN_TW - 1), ty = tid / ZN_TW;   // pixels (c, ty) and (c, ty + 8) of the tile
+    const int col = x0 + c;
+    const size_t P = (size_t)p.W * p.H;
+    const float hix = ZN_MAGIC + 132.0f + 256.0f * (float)p.W, hiy = ZN_MAGIC + 132.0f + 256.0f * (float)p.H;
+    uint32_t best[2] = {0u, 0u};
+    int bi[2] = {-1, -1};
+    for (int d0 = 0; d0 < p.D; d0 += ZN_PC) {
+        const int n = min(ZN_PC, p.D - d0);   // (uniform: the barriers below are reached by every thread or by none)
+        BkList<KMAX> acc[2][ZN_PC];
+#pragma unroll
+        for (int k = 0; k < ZN_PC; k++) {
+            acc[0][k].clear();
+            acc[1][k].clear();
+        }
+        for (int v = p.v0; v < p.v0 + p.vcount; v++) {
+            const float *q = p.Q + 12 * v;
+            Affine A[S::NS];
+#pragma unroll
+            for (int s = 0; s < S::NS; s++) A[s] = view_affine(q, sxn[s], syn[s]);
+            const uint32_t *qv = p.quads + p.pad_slab * (size_t)(p.view_slot ? p.view_slot[v] : v);
+#pragma unroll
+            for (int k = 0; k < ZN_PC; k++) {
+                if (k >= n) break;
+                const float delta = p.z[d0 + k];
+                float zs[S::NS];   // the plane of every sample position; NaN: dead
+#pragma unroll
+                for (int s = 0; s < S::NS; s++) {
+                    const float z = sz0[s] + delta;   // one add (section 19 rule 2)
+                    zs[s] = (z > -1.0f && z < 1.0f) ? z : __builtin_nanf("");
+                }
+                if constexpr (!WINDOW) {
+                    // c = e(p): sample s is pixel (c, ty + 8 s)
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        const uint32_t e = absdiff_sample(A[h], q[2], q[6], q[10], zs[h], qv, (uint32_t)p.pitch, hix, hiy, lut, sa[h]);
+                        acc[h][k].insert(e ? e & 0xffffffu : BK_NONE);
+                    }
+                } else {
+#pragma unroll
+                    for (int s = 0; s < S::NS; s++) {
+                        const int i = tid + ZN_THREADS * s;
+                        Elem e;
+                        if constexpr (ZNCC)
+                            e = zncc_sample(A[s], q[2], q[6], q[10], zs[s], qv, (uint32_t)p.pitch, hix, hiy, lut, sa[s], saa[s]);
+                        else
+                            e = absdiff_sample(A[s], q[2], q[6], q[10], zs[s], qv, (uint32_t)p.pitch, hix, hiy, lut, sa[s]);
+                        if (i < S::SAMPLES) smp[i] = e;
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int t = 0; t < S::NR; t++) {
+                        const int j = tid + ZN_THREADS * t;   // row sum (hy, cc) = (j / 32, j % 32): elements cc .. cc + 2R of row hy
+                        if (j < S::ROWSUMS) {
+                            const Elem *src = smp + (j / ZN_TW) * S::HW + (j & (ZN_TW - 1));
+                            Elem sum = src[0];
+#pragma unroll
+                            for (int e = 1; e <= 2 * R; e++) sum = C::add(sum, src[e]);
+                            rows[j] = sum;
+                        }
+                    }
+                    // ok(p) of the thread's own pixels: read here, the samples are rewritten behind the next barrier
+                    const uint32_t ok0 = C::ok(smp[(ty + R) * S::HW + c + R]), ok1 = C::ok(smp[(ty + 8 + R) * S::HW + c + R]);
+                    __syncthreads();
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        const Elem *src = rows + (ty + 8 * h) * ZN_TW + c;   // rows ty + 8h .. + 2R of the halo = the window of tile row ty + 8h
+                        Elem sum = src[0];
+#pragma unroll
+                        for (int e = 1; e <= 2 * R; e++) sum = C::add(sum, src[e * ZN_TW]);
+                        acc[h][k].insert(C::cost(sum, h ? ok1 : ok0));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int row = y0 + ty + 8 * h;
+            if (col < p.W && row < p.H) {
+                const size_t pix = (size_t)row * p.W + col;
+#pragma unroll
+                for (int k = 0; k < ZN_PC; k++)
+                    if (k < n) {
+                        const uint32_t cell = acc[h][k].cell(keep);
+                        if (write_volume) __builtin_nontemporal_store(cell, p.volume + (size_t)(d0 + k) * P + pix);  // written once, read by a later kernel
+                        if (fused) argmin_update_packed<CS_FIXED>(cell, d0 + k, best[h], bi[h]);
+                    }
+            }
+        }
+    }
+    if (fused) {
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int row = y0 + ty + 8 * h;
+            if (col < p.W && row < p.H) store_best<CS_FIXED>(p, (size_t)row * p.W + col, best[h] & 0xffffffu, best[h] >> 24, bi[h]);   // depth = delta[index]: an offset
+        }
+    }
+}
+
+template <int COST, int R>
+void band_bestk_launch(mvs_ctx *ctx, const SweepParams &p, const float *prior, int keep, bool vol, bool fused)
+{
+    const dim3 grid((unsigned)div_up(ctx->W, ZN_TW), (unsigned)div_up(ctx->H, ZN_TH));
+    const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
+    if (keep == MVS_KEEP_ALL)
+        sweep_fx_band_bestk<COST, R, 0><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, prior, keep, vol, fused);
+    else if (keep <= 2)
+        sweep_fx_band_bestk<COST, R, 2><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, prior, keep, vol, fused);
+    else if (keep <= 4)
+        sweep_fx_band_bestk<COST, R, 4><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, prior, keep, vol, fused);
+    else
+        sweep_fx_band_bestk<COST, R, 8><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, prior, keep, vol, fused);
+}
+
+template <int COST>
+void band_bestk_launch_radius(mvs_ctx *ctx, const SweepParams &p, const float *prior, int radius, int keep, bool vol, bool fused)
+{
+    switch (radius) {
+    case 0:
+        if constexpr (COST == MVS_COST_ABSDIFF) band_bestk_launch<COST, 0>(ctx, p, prior, keep, vol, fused);   // (refused for ZNCC by the caller)
+        break;
+    case 1: band_bestk_launch<COST, 1>(ctx, p, prior, keep, vol, fused); break;
+    case 2: band_bestk_launch<COST, 2>(ctx, p, prior, keep, vol, fused); break;
+    case 3: band_bestk_launch<COST, 3>(ctx, p, prior, keep, vol, fused); break;
+    default: band_bestk_launch<COST, 4>(ctx, p, prior, keep, vol, fused); break;
+    }
+}
+
+}  // namespace
+
+}  // namespace mvs
+
+using namespace mvs;
+
+int mvs_sweep_run_band_bestk(mvs_ctx *ctx, int view_first, int view_count, const void *prior_dev, int cost, int radius, int keep, unsigned flags)
+{
+    static const char who[] = "mvs_sweep_run_band_bestk";
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
+    if (!prior_dev) return fail(ctx, MVS_EINVAL, "%s: prior_dev is null", who);
+    if (cost != MVS_COST_ABSDIFF && cost != MVS_COST_ZNCC) return fail(ctx, MVS_EINVAL, "%s: unknown cost %d", who, cost);
+    const int rmin = cost == MVS_COST_ZNCC ? 1 : 0;
+    if (radius < rmin || radius > 4) return fail(ctx, MVS_EINVAL, "%s: radius %d outside %d..4", who, radius, rmin);
+    if (keep < 0 || keep > 8) return fail(ctx, MVS_EINVAL, "%s: keep %d outside 1..8 and not MVS_KEEP_ALL", who, keep);
+    bool vol, fused;
+    int rc;
+    if ((rc = fx_sweep_preconditions(ctx, who, view_first, view_count, flags, vol, fused))) return rc;
+    for (int d = 0; d < ctx->D; d++)
+        if (!(ctx->z_host[d] > -1.0f && ctx->z_host[d] < 1.0f))
+            return fail(ctx, MVS_ESTATE, "%s: the plane table holds the band's offsets and must lie inside (-1, 1): offset %d is %g", who, d, ctx->z_host[d]);
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)ctx->W * ctx->H;
+    if ((rc = sweep_outputs(ctx, vol, who))) return rc;
+    if ((rc = ensure(ctx, ctx->band_prior, P * sizeof(float)))) return rc;
+    if ((rc = ensure_fx_lut(ctx))) return rc;
+    // the context's own copy: the caller's map may be the depth map this run overwrites (stream order puts the copy first)
+    if (prior_dev != ctx->band_prior.ptr) MVS_HIP(ctx, hipMemcpyAsync(ctx->band_prior.ptr, prior_dev, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    SweepParams p;
+    fill_params(ctx, p, view_first, view_count, ZN_TH, ZN_PC);
+    const float *prior = (const float *)ctx->band_prior.ptr;
+    {
+        ProfileScope ps(ctx, MVS_K_SWEEP);
+        if (cost == MVS_COST_ZNCC)
+            band_bestk_launch_radius<MVS_COST_ZNCC>(ctx, p, prior, radius, keep, vol, fused);
+        else
+            band_bestk_launch_radius<MVS_COST_ABSDIFF>(ctx, p, prior, radius, keep, vol, fused);
+    }
+    MVS_HIP(ctx, hipGetLastError());
+    ctx->band_planes = ctx->D;   // the band state, exactly as mvs_sweep_run_band leaves it
+    ctx->band_resolved = false;
+    fused ? note_full_selection(ctx) : note_no_selection(ctx);
+    return MVS_OK;
+}

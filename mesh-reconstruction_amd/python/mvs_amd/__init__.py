@@ -142,6 +142,7 @@ ABI = [
     ("mvs_sweep_band_report", _i, [_vp, C.POINTER(_i)]),
     ("mvs_sweep_run_zncc", _i, [_vp, _i, _i, _i, C.c_uint]),
     ("mvs_sweep_run_bestk", _i, [_vp, _i, _i, _i, _i, _i, C.c_uint]),
+    ("mvs_sweep_run_band_bestk", _i, [_vp, _i, _i, _vp, _i, _i, _i, C.c_uint]),
     ("mvs_pyramid_downsample_device", _i, [_vp, _vp, _vp, _i]),
     ("mvs_pyramid_stage", _i, [_vp, _vp]),
     ("mvs_pyramid_prior", _i, [_vp, _vp, _vp, _i]),
@@ -440,7 +441,18 @@ def _filter_step(ctx, depth_ptr, filter, step, fetch=False):
     return out if fetch else ctx.depth_filtered_pointer()
 
 
-def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, fetch=True, filter=None):
+def _cost_args(cost):
+    """the `cost` keyword of the coarse-to-fine helpers: dict(cost="zncc" | "absdiff", radius=, keep=) -> (MVS_COST_*, radius, keep)"""
+    unknown = set(cost) - {"cost", "radius", "keep"}
+    if unknown:
+        raise ValueError("cost: unknown keys %s (cost, radius, keep)" % sorted(unknown))
+    kinds = {"zncc": MVS_COST_ZNCC, "absdiff": MVS_COST_ABSDIFF}
+    if cost.get("cost", "zncc") not in kinds:
+        raise ValueError("cost: %r is neither \"zncc\" nor \"absdiff\"" % (cost.get("cost"),))
+    return kinds[cost.get("cost", "zncc")], int(cost.get("radius", 2)), int(cost.get("keep", MVS_KEEP_ALL))
+
+
+def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, fetch=True, filter=None, cost=None):
     """Two-level sweep on the inputs staged on `ctx` (main view and side views; fixed sampler): `coarse_planes` planes over [z_lo, z_hi],
     refined; then `band_planes` planes within +- band_steps coarse steps of that map (mvs_sweep_run_band with the context's own depth map
     as the prior), refined and resolved.  Pure composition of Context calls -> the absolute depth map (H, W) float32 (fetch=False: None,
@@ -449,17 +461,30 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     coarse depth confines the band to the wrong place: this lowers the median error, not the outliers.
     filter: None, or dict(radius=, tau=, max_steps=): the coarse map is filtered (Context.depth_filter, median then mean, the guide the
     staged main image) before it becomes the band's prior, and so is the resolved map; the depth gate is max_steps plane steps of the
-    level that selected the map.  The filtered resolved map is returned (fetch=False: it stays at depth_filtered_pointer())."""
+    level that selected the map.  The filtered resolved map is returned (fetch=False: it stays at depth_filtered_pointer()).
+    cost: None (the calls above), or dict(cost="zncc" | "absdiff", radius=2, keep=MVS_KEEP_ALL): the windowed matching cost of both
+    levels: the coarse level runs sweep_run_bestk, the band level sweep_run_band_bestk; "zncc" is the one for
+    frames whose exposure drifts.  Use it WITH filter=: every window member is sampled at its own prior, so an outlier of a raw coarse
+    map spoils the windows of its neighbours too.  On the exposure scene at 160 x 100 (ZNCC, radius 3, bad = more than 1.5 steps of a
+    48-plane table off): 48 global ZNCC planes 1.06 % bad; 16 + 32 planes on the raw prior 3.7 %, on the filtered prior 0.14 %,
+    what 128 global planes give."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     ctx.sweep_set_planes(coarse_planes, z_lo, z_hi)
-    ctx.sweep_run(0, None, flags)
+    if cost is None:
+        ctx.sweep_run(0, None, flags)
+    else:
+        cost = _cost_args(cost)
+        ctx.sweep_run_bestk(*cost, 0, None, flags)
     ctx.sweep_refine_depth()
     prior = ctx.sweep_result_pointers()[0]
     if filter is not None:
         prior = _filter_step(ctx, prior, filter, (float(z_hi) - float(z_lo)) / coarse_planes)
     hb = float(np.float32(band_steps * (float(z_hi) - float(z_lo)) / coarse_planes))
     ctx.sweep_set_planes(band_planes, -hb, hb)
-    ctx.sweep_run_band(prior, 0, None, flags)
+    if cost is None:
+        ctx.sweep_run_band(prior, 0, None, flags)
+    else:
+        ctx.sweep_run_band_bestk(prior, *cost, 0, None, flags)
     ctx.sweep_refine_depth()
     if filter is None:
         return ctx.sweep_band_resolve(fetch=fetch)
@@ -468,7 +493,7 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     return out if fetch else None
 
 
-def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, tau=255, fetch=True, filter=None):
+def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, tau=255, fetch=True, filter=None, cost=None):
     """Coarse-to-fine over a resolution pyramid: ctxs = [fine, half] or [fine, half, quarter], each level a context
     of exactly half the size of the one before it, on one GPU, with the inputs staged on ctxs[0].  Stages down the chain (pyramid_stage);
     coarsest level: `coarse_planes` planes over [z_lo, z_hi], refined; each finer level: its prior from the level below (pyramid_prior with
@@ -479,12 +504,19 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
     filter: None, or dict(radius=, tau=, max_steps=): each level's upsampled prior is filtered on that level (Context.depth_filter, median
     then mean, the guide the level's staged main image) before its band run, and so is the finest level's resolved map, which is then what
     is returned (fetch=False: it stays at ctxs[0].depth_filtered_pointer()); the depth gate is max_steps plane steps of the level that
-    selected the map."""
+    selected the map.
+    cost: None (the calls above), or dict(cost="zncc" | "absdiff", radius=2, keep=MVS_KEEP_ALL) as in coarse_to_fine: the coarsest level
+    runs sweep_run_bestk and every band level sweep_run_band_bestk, the radius in pixels of each level.  As there, a raw prior makes the
+    windowed band worse than the global windowed sweep (3.7 % against 1.06 % bad pixels on the exposure scene): use it with filter=."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     for above, below in zip(ctxs, ctxs[1:]):
         above.pyramid_stage(below)
     ctxs[-1].sweep_set_planes(coarse_planes, z_lo, z_hi)
-    ctxs[-1].sweep_run(0, None, flags)
+    if cost is None:
+        ctxs[-1].sweep_run(0, None, flags)
+    else:
+        cost = _cost_args(cost)
+        ctxs[-1].sweep_run_bestk(*cost, 0, None, flags)
     ctxs[-1].sweep_refine_depth()
     step = (float(z_hi) - float(z_lo)) / coarse_planes
     depth_ptr, out = None, None            # None: the depth map of the level below
@@ -496,7 +528,10 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
             prior = _filter_step(ctx, prior, filter, step)
         hb = float(np.float32(band_steps * step))
         ctx.sweep_set_planes(band_planes, -hb, hb)
-        ctx.sweep_run_band(prior, 0, None, flags)
+        if cost is None:
+            ctx.sweep_run_band(prior, 0, None, flags)
+        else:
+            ctx.sweep_run_band_bestk(prior, *cost, 0, None, flags)
         ctx.sweep_refine_depth()
         out = ctx.sweep_band_resolve(fetch=fetch and level == 0 and filter is None)
         depth_ptr = ctx.sweep_band_pointers()[0]
@@ -1219,6 +1254,18 @@ class Context:
         if view_count is None:
             view_count = self.V - view_first
         self._check(self.lib.mvs_sweep_run_bestk(self.h, int(view_first), int(view_count), int(cost), int(radius), int(keep), int(flags)))
+
+    def sweep_run_band_bestk(self, prior_ptr, cost, radius=2, keep=MVS_KEEP_ALL, view_first=0, view_count=None, flags=MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN):
+        """mvs_sweep_run_band_bestk: sweep_run_bestk with plane d of pixel q at prior(q) + delta_d, delta = the staged plane table
+        (sweep_set_planes(D, -hb, +hb)); every window member is sampled at its own prior.  cost MVS_COST_ZNCC (radius 1..4) or
+        MVS_COST_ABSDIFF (radius 0..4), keep 1..8 or MVS_KEEP_ALL (with MVS_COST_ZNCC: the ZNCC band sweep).  prior_ptr: device address
+        of H*W float32, e.g. sweep_result_pointers()[0], sweep_band_pointers()[1], depth_filtered_pointer().  It leaves the band state
+        of sweep_run_band: the depth map holds OFFSETS until sweep_band_resolve.  Filter a raw coarse prior first: its outliers stay
+        outliers and spoil their neighbours' windows (asynchronous, stream-ordered)"""
+        if view_count is None:
+            view_count = self.V - view_first
+        self._check(self.lib.mvs_sweep_run_band_bestk(self.h, int(view_first), int(view_count), C.c_void_p(int(prior_ptr)) if prior_ptr else None, int(cost),
+                                                      int(radius), int(keep), int(flags)))
 
     # ---- depth-map filter (include/mvs.h, DESIGN.md section 23) -----------------------------------
     def depth_filter(self, depth_ptr, radius=4, tau=255, max_step=float("inf"), guide_ptr=None, median=True, mean=True, fill=0, fetch=True):
