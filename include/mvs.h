@@ -522,6 +522,68 @@ int mvs_depth_filter(mvs_ctx *ctx, const void *depth_dev, const void *guide_dev 
                      unsigned flags);
 void *mvs_depth_filtered_device(mvs_ctx *ctx);
 int mvs_depth_filter_fetch(mvs_ctx *ctx, float *depth_hw);
+/* Hypothesis propagation: PatchMatch refinement of a depth map (csrc/propagate.hip; DESIGN.md section 25 is the contract; bit-identical
+ * to tests/propagate_mirror.py).  Every other estimator scores the hypotheses of a plane table; here every pixel carries a depth and a
+ * slope, tests the hypotheses of its neighbours and a few perturbations of its own, and keeps what matches best: good hypotheses spread
+ * into bad regions, depth is continuous, the window lies on a slanted plane and no D x H x W volume exists.  Fixed sampler only.  All f32
+ * arithmetic below has one rounding per operation and no FMA, except inside the sampler.
+ *   State per pixel p: a hypothesis (z, gx, gy) -- NDC depth at the pixel centre, its change per column and per row -- and a packed cell
+ * k << 24 | sum in mvs_sweep_run_bestk's format.  p has a hypothesis when -1 < z < 1; without one it holds exactly MVS_BACKGROUND_DEPTH,
+ * 0, 0 and cell 0.
+ *   1. Member depth: for the hypothesis (z, gx, gy) at p and window member q, dc = q.col - p.col, dr = q.row - p.row:
+ *      z_q = (z + gx (float)dc) + gy (float)dr.  q is live when it is inside the frame and -1 < z_q < 1 (false for NaN).
+ *   2. Sample: ok(q) and dot(q) of view v are the fixed sampler's sample of mvs_sweep_run at (xn(q), yn(q), z_q), bit for bit; a member
+ *      that is not live is not ok.
+ *   3. Per-view cost and cell: rules 1 and 2 of mvs_sweep_run_bestk on those samples -- MVS_COST_ZNCC (radius 1..4) or MVS_COST_ABSDIFF
+ *      (radius 0..4), keep 1..8 or MVS_KEEP_ALL -- over the views [view_first, view_first + view_count) given to init.  The plane table
+ *      is not read and not required.
+ *   4. Better: cell c beats cell b iff c >> 24 != 0 and (b == 0 or s_c k_b < s_b k_c): the depth selection's rule.  It is strict, so a
+ *      tie keeps the earlier hypothesis.
+ *   5. mvs_propagate_init copies depth_dev (H * W f32 on the context's GPU: any map in the library's depth convention, or the stage's own
+ *      z map) into z, invalid values as MVS_BACKGROUND_DEPTH.  Slopes are 0; with MVS_PROPAGATE_SLOPES gx = (z(col + 1) - z(col - 1)) 0.5f
+ *      when both neighbours are usable, else the one-sided difference z(col + 1) - z(col) or z(col) - z(col - 1), else 0, and gy likewise
+ *      along rows; a neighbour is usable when it has a hypothesis and fabsf(z_n - z_p) <= max_step (INFINITY: no gate; max_step is
+ *      ignored without the flag but must not be negative or NaN).  Then every pixel's cell is evaluated (rules 1-3), cost, radius, keep
+ *      and the view range are recorded and the iteration counter is set to 0.
+ *   6. mvs_propagate_run runs `iterations` >= 1 iterations.  Iteration t, counted from init, has the halves h = 0, 1; in half h the
+ *      pixels with (row + col + h) & 1 == 0 are active.  They read neighbours at odd Manhattan distance only, which are inactive, so a
+ *      half is free of races in place.  An active pixel walks this list and takes every candidate that is better (rule 4) than what it
+ *      holds at that moment:
+ *        near: the offsets (dc, dr) = (-1, 0), (1, 0), (0, -1), (0, 1); far: (-5, 0), (5, 0), (0, -5), (0, 5).  If n = p + (dc, dr) is
+ *          inside the frame and has a hypothesis, whatever its cell, the candidate is z' = (z_n - gx_n (float)dc) - gy_n (float)dr with
+ *          gx_n, gy_n: the neighbour's plane extended to p.
+ *        random j = 0 .. nrandom - 1 (nrandom 0..4), only if the pixel has a hypothesis by now: z' = z + dz_t u0, gx' = gx + dg_t u1,
+ *          gy' = gy + dg_t u2 from the pixel's CURRENT hypothesis; dz_t is dz halved t times (dz_t = dz_(t-1) * 0.5f), dg_t likewise;
+ *          u_c = ((float)(int32)(x >> 8) - 8388608.0f) * (1.0f / 8388608.0f) with
+ *          x = mix(mix(mix(seed + (2 t + h)) ^ (row W + col)) ^ (4 j + c)) in u32 arithmetic and
+ *          mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *      A candidate whose centre is not live has no counted view, hence cell 0, and never wins.  For every active pixel of every half the
+ *      call counts the class of what the pixel holds at the end of its list: kept / near / far / random.  Consequence: run(a) then run(b)
+ *      with the same dz, dg, nrandom and seed equals run(a + b).
+ *   7. Outputs: mvs_propagate_fetch downloads z, gx, gy and the cells (each pointer may be NULL; synchronises).
+ *      mvs_propagate_depth_device is the z map, a depth map in the library's convention: it feeds mvs_depth_upload_device,
+ *      mvs_depth_filter, the band sweeps as a prior, mvs_pyramid_prior and mvs_tsdf_shade.  mvs_propagate_cost_device is the cells as
+ *      mean costs, (float)sum / (float)(255 k), +inf for cell 0, refreshed by init and run.  Both are NULL before the first init and do
+ *      not change afterwards.  mvs_propagate_report: out[0..3] = kept, near, far, random since init, out[4] = the pixels that hold a
+ *      cell != 0 now; it synchronises.
+ * It propagates the preference of a window across a depth step for the nearer surface as well: beside occluders it does not help and
+ * random steps of a coarse plane step make it worse (DESIGN.md section 25 has the figures).
+ *   The stage touches no sweep, band, selection or filter state; it reads the staged frames however they got there (host setters,
+ * _device forms, frame-store slots).  Its maps -- five H * W maps and the counters -- are allocated by the first mvs_propagate_init; a
+ * context that never calls it allocates nothing.  Asynchronous on the context's stream (one launch per half, no host synchronisation),
+ * timed under MVS_K_SWEEP.
+ * Errors: MVS_EINVAL for a NULL ctx, depth_dev or out, an unknown cost, a radius outside the cost's range, keep outside 0..8, a view
+ * range outside 0..V, unknown flag bits, a negative or NaN max_step, iterations < 1, nrandom outside 0..4, a negative or non-finite dz or
+ * dg; MVS_ESTATE without main view or views, for the exact sampler, for run, fetch and report before init, and for run when fewer views
+ * are staged than init's range needs; MVS_ENOMEM.  All checks come before the first allocation; after an error nothing is written and the
+ * context stays usable. */
+#define MVS_PROPAGATE_SLOPES 1u
+int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int view_count, int cost, int radius, int keep, float max_step, unsigned flags);
+int mvs_propagate_run(mvs_ctx *ctx, int iterations, float dz, float dg, int nrandom, unsigned seed);
+int mvs_propagate_fetch(mvs_ctx *ctx, float *z_hw, float *gx_hw, float *gy_hw, unsigned int *cells_hw);
+void *mvs_propagate_depth_device(mvs_ctx *ctx);
+void *mvs_propagate_cost_device(mvs_ctx *ctx);
+int mvs_propagate_report(mvs_ctx *ctx, long long out[5]);
 /* The same selection in two steps, for a view-sharded job that REDUCE-SCATTERS the packed volume instead of all-reducing it
  * (half the bytes over xGMI): rank r owns the summed cells of planes [plane_first, plane_first + plane_count) in
  * `volume_slice_dev` ([plane_count][H][W] u32) and selects a partial best per pixel over them -- `partial_out_dev` receives

@@ -222,6 +222,13 @@ struct mvs_ctx {
     // each, one allocation made by the first call; dfilter_have: a call has written the filtered map
     mvs::DevBuf dfilter_maps;
     bool dfilter_have = false;
+    // hypothesis propagation (propagate.hip: mvs_propagate_init / mvs_propagate_run): z, gx, gy (H*W f32 each), the packed cells (H*W u32)
+    // and the cost map (H*W f32) in one allocation, and the report's four 64-bit counters, both made by the first init; prop_have: an init
+    // has run; what it recorded (cost, radius, keep, the view range) and the iterations run since
+    mvs::DevBuf prop_maps, prop_counters;
+    bool prop_have = false;
+    int prop_cost = 0, prop_radius = 0, prop_keep = 0, prop_view_first = 0, prop_view_count = 0;
+    long long prop_iter = 0;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

@@ -28,6 +28,7 @@ MVS_CLEAN_SCORES_AGGREGATED = 1
 MVS_WINDOW_SELECT, MVS_WINDOW_REFINE = 1, 2
 MVS_VOLUME_RAW, MVS_VOLUME_WINDOWED = 0, 1
 MVS_FILTER_MEDIAN, MVS_FILTER_MEAN, MVS_FILTER_FILL = 1, 2, 4
+MVS_PROPAGATE_SLOPES = 1
 VOLUME_SOURCES = {"raw": MVS_VOLUME_RAW, "windowed": MVS_VOLUME_WINDOWED}
 MVS_SHARD_ROWS, MVS_SHARD_VIEWS, MVS_SHARD_VIEWS_SCATTER = 0, 1, 2
 SHARD_MODES = {"rows": 0, "views": 1, "views_scatter": 2}
@@ -149,6 +150,12 @@ ABI = [
     ("mvs_depth_filter", _i, [_vp, _vp, _vp, _i, _i, _f, _i, C.c_uint]),
     ("mvs_depth_filtered_device", _vp, [_vp]),
     ("mvs_depth_filter_fetch", _i, [_vp, _fp]),
+    ("mvs_propagate_init", _i, [_vp, _vp, _i, _i, _i, _i, _i, _f, C.c_uint]),
+    ("mvs_propagate_run", _i, [_vp, _i, _f, _f, _i, C.c_uint]),
+    ("mvs_propagate_fetch", _i, [_vp, _fp, _fp, _fp, C.POINTER(C.c_uint32)]),
+    ("mvs_propagate_depth_device", _vp, [_vp]),
+    ("mvs_propagate_cost_device", _vp, [_vp]),
+    ("mvs_propagate_report", _i, [_vp, C.POINTER(C.c_longlong)]),
     ("mvs_sweep_argmin_partial", _i, [_vp, _vp, _i, _i, _vp]),
     ("mvs_sweep_combine_partials", _i, [_vp, _vp, _i]),
     ("mvs_sweep_volume_device", _vp, [_vp, C.POINTER(_sz)]),
@@ -452,7 +459,22 @@ def _cost_args(cost):
     return kinds[cost.get("cost", "zncc")], int(cost.get("radius", 2)), int(cost.get("keep", MVS_KEEP_ALL))
 
 
-def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, fetch=True, filter=None, cost=None):
+def _propagate_step(ctx, depth_ptr, propagate, cost, step, fetch):
+    """the `propagate` keyword of the coarse-to-fine helpers: propagate_init + propagate_run on the map at depth_ptr with the windowed cost
+    `cost` = (MVS_COST_*, radius, keep); the random steps are dz_steps / dg_steps plane steps `step` of the level that selected the map
+    -> the z map (fetch) or None (it stays at propagate_depth_pointer())"""
+    unknown = set(propagate) - {"iterations", "dz_steps", "dg_steps", "nrandom", "seed", "slopes"}
+    if unknown:
+        raise ValueError("propagate: unknown keys %s (iterations, dz_steps, dg_steps, nrandom, seed, slopes)" % sorted(unknown))
+    if cost is None:
+        raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
+    ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
+    ctx.propagate_run(int(propagate.get("iterations", 3)), float(np.float32(float(propagate.get("dz_steps", 0.5)) * step)),
+                      float(np.float32(float(propagate.get("dg_steps", 0.125)) * step)), int(propagate.get("nrandom", 2)), int(propagate.get("seed", 0)))
+    return ctx.propagate_fetch()[0] if fetch else None
+
+
+def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, fetch=True, filter=None, cost=None, propagate=None):
     """Two-level sweep on the inputs staged on `ctx` (main view and side views; fixed sampler): `coarse_planes` planes over [z_lo, z_hi],
     refined; then `band_planes` planes within +- band_steps coarse steps of that map (mvs_sweep_run_band with the context's own depth map
     as the prior), refined and resolved.  Pure composition of Context calls -> the absolute depth map (H, W) float32 (fetch=False: None,
@@ -467,8 +489,16 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     frames whose exposure drifts.  Use it WITH filter=: every window member is sampled at its own prior, so an outlier of a raw coarse
     map spoils the windows of its neighbours too.  On the exposure scene at 160 x 100 (ZNCC, radius 3, bad = more than 1.5 steps of a
     48-plane table off): 48 global ZNCC planes 1.06 % bad; 16 + 32 planes on the raw prior 3.7 %, on the filtered prior 0.14 %,
-    what 128 global planes give."""
+    what 128 global planes give.
+    propagate: None (the calls above), or dict(iterations=3, dz_steps=0.5, dg_steps=0.125, nrandom=2, seed=0, slopes=False), which needs
+    cost=: the map that would be returned becomes the start of Context.propagate_init / propagate_run with that cost (DESIGN.md section
+    25; the random steps in plane steps of the band level), and the propagated z map is returned in its place (fetch=False: it stays at
+    propagate_depth_pointer()).  It replaces outliers by their neighbours' hypotheses.  WARNING: it does not help beside depth steps: a
+    window across a step prefers the nearer surface and propagation spreads that preference (on section 22's occluder scene the bad share
+    of the edge pixels does not fall, and random steps of a coarse plane step raise it)."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
+    if propagate is not None and cost is None:
+        raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
     ctx.sweep_set_planes(coarse_planes, z_lo, z_hi)
     if cost is None:
         ctx.sweep_run(0, None, flags)
@@ -486,6 +516,12 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     else:
         ctx.sweep_run_band_bestk(prior, *cost, 0, None, flags)
     ctx.sweep_refine_depth()
+    if propagate is not None:
+        ctx.sweep_band_resolve(fetch=False)
+        final = ctx.sweep_band_pointers()[0]
+        if filter is not None:
+            final = _filter_step(ctx, final, filter, 2.0 * hb / band_planes)
+        return _propagate_step(ctx, final, propagate, cost, 2.0 * hb / band_planes, fetch)
     if filter is None:
         return ctx.sweep_band_resolve(fetch=fetch)
     ctx.sweep_band_resolve(fetch=False)
@@ -493,7 +529,7 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     return out if fetch else None
 
 
-def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, tau=255, fetch=True, filter=None, cost=None):
+def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z_hi=1.0, tau=255, fetch=True, filter=None, cost=None, propagate=None):
     """Coarse-to-fine over a resolution pyramid: ctxs = [fine, half] or [fine, half, quarter], each level a context
     of exactly half the size of the one before it, on one GPU, with the inputs staged on ctxs[0].  Stages down the chain (pyramid_stage);
     coarsest level: `coarse_planes` planes over [z_lo, z_hi], refined; each finer level: its prior from the level below (pyramid_prior with
@@ -507,8 +543,14 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
     selected the map.
     cost: None (the calls above), or dict(cost="zncc" | "absdiff", radius=2, keep=MVS_KEEP_ALL) as in coarse_to_fine: the coarsest level
     runs sweep_run_bestk and every band level sweep_run_band_bestk, the radius in pixels of each level.  As there, a raw prior makes the
-    windowed band worse than the global windowed sweep (3.7 % against 1.06 % bad pixels on the exposure scene): use it with filter=."""
+    windowed band worse than the global windowed sweep (3.7 % against 1.06 % bad pixels on the exposure scene): use it with filter=.
+    propagate: None (the calls above), or dict(iterations=, dz_steps=, dg_steps=, nrandom=, seed=, slopes=) as in coarse_to_fine, which
+    needs cost=: the finest level's final map becomes the start of ctxs[0].propagate_init / propagate_run and the propagated z map is
+    returned in its place (fetch=False: it stays at ctxs[0].propagate_depth_pointer()).  WARNING, as there: propagation does not help
+    beside depth steps, where a window prefers the nearer surface; it spreads that preference."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
+    if propagate is not None and cost is None:
+        raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
     for above, below in zip(ctxs, ctxs[1:]):
         above.pyramid_stage(below)
     ctxs[-1].sweep_set_planes(coarse_planes, z_lo, z_hi)
@@ -533,12 +575,17 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
         else:
             ctx.sweep_run_band_bestk(prior, *cost, 0, None, flags)
         ctx.sweep_refine_depth()
-        out = ctx.sweep_band_resolve(fetch=fetch and level == 0 and filter is None)
+        out = ctx.sweep_band_resolve(fetch=fetch and level == 0 and filter is None and propagate is None)
         depth_ptr = ctx.sweep_band_pointers()[0]
         step = 2.0 * hb / band_planes
     if filter is not None and len(ctxs) > 1:
-        out = _filter_step(ctxs[0], depth_ptr, filter, step, fetch=fetch)
-        out = out if fetch else None
+        out = _filter_step(ctxs[0], depth_ptr, filter, step, fetch=fetch and propagate is None)
+        out = out if fetch and propagate is None else None
+        depth_ptr = ctxs[0].depth_filtered_pointer()
+    if propagate is not None:
+        if depth_ptr is None:
+            depth_ptr = ctxs[0].sweep_result_pointers()[0]      # one level: the refined global sweep's map
+        out = _propagate_step(ctxs[0], depth_ptr, propagate, cost, step, fetch)
     return out
 
 
@@ -1289,6 +1336,48 @@ class Context:
     def depth_filtered_pointer(self):
         """device address of the filtered map of the last depth_filter (0 before the first)"""
         return self.lib.mvs_depth_filtered_device(self.h) or 0
+
+    # ---- hypothesis propagation (include/mvs.h, DESIGN.md section 25) ----------------------------
+    def propagate_init(self, depth_ptr, cost, radius=2, keep=MVS_KEEP_ALL, view_first=0, view_count=None, slopes=False, max_step=float("inf")):
+        """mvs_propagate_init: every pixel gets the hypothesis (z, gx, gy) -- z from the H*W float32 depth map at device address depth_ptr
+        (sweep_result_pointers()[0], sweep_band_pointers()[0], depth_filtered_pointer(), propagate_depth_pointer(), ...), the slopes 0 or,
+        with `slopes`, the map's differences between neighbours no more than max_step apart -- and the packed cell of that hypothesis
+        under the windowed cost (MVS_COST_ZNCC radius 1..4, MVS_COST_ABSDIFF radius 0..4; keep 1..8 or MVS_KEEP_ALL) over the given side
+        views.  Fixed sampler; no plane table is needed (asynchronous, stream-ordered)"""
+        if view_count is None:
+            view_count = self.V - view_first
+        self._check(self.lib.mvs_propagate_init(self.h, C.c_void_p(int(depth_ptr)) if depth_ptr else None, int(view_first), int(view_count), int(cost), int(radius),
+                                                int(keep), float(max_step), MVS_PROPAGATE_SLOPES if slopes else 0))
+
+    def propagate_run(self, iterations, dz, dg, nrandom=2, seed=0):
+        """mvs_propagate_run: `iterations` PatchMatch iterations on the hypotheses of propagate_init.  In each of an iteration's two
+        checkerboard halves an active pixel tests the planes of its neighbours at distance 1 and 5 and `nrandom` (0..4) perturbations of
+        what it holds (depth within +-dz, slopes within +-dg, both halved every iteration) and keeps what matches better.  Outliers are
+        replaced by their neighbours' hypotheses; the cost's minimum is not sharpened.  Beside depth steps it does NOT help: a window
+        across a step prefers the nearer surface and propagation spreads that preference (DESIGN.md section 25 has the figures).
+        run(a) then run(b) with the same arguments is run(a + b) (asynchronous, stream-ordered)"""
+        self._check(self.lib.mvs_propagate_run(self.h, int(iterations), float(dz), float(dg), int(nrandom), int(seed) & 0xffffffff))
+
+    def propagate_fetch(self):
+        """mvs_propagate_fetch -> (z, gx, gy (H, W) float32, cells (H, W) uint32: k << 24 | sum); synchronises"""
+        z, gx, gy = (np.empty((self.H, self.W), np.float32) for _ in range(3))
+        cells = np.empty((self.H, self.W), np.uint32)
+        self._check(self.lib.mvs_propagate_fetch(self.h, _ptr(z, _fp), _ptr(gx, _fp), _ptr(gy, _fp), _ptr(cells, C.POINTER(C.c_uint32))))
+        return z, gx, gy, cells
+
+    def propagate_depth_pointer(self):
+        """device address of the z map, a depth map in the library's convention (0 before the first propagate_init)"""
+        return self.lib.mvs_propagate_depth_device(self.h) or 0
+
+    def propagate_cost_pointer(self):
+        """device address of the mean-cost map of the cells, +inf for cell 0 (0 before the first propagate_init)"""
+        return self.lib.mvs_propagate_cost_device(self.h) or 0
+
+    def propagate_report(self):
+        """mvs_propagate_report -> [kept, near, far, random since propagate_init, pixels holding a cell != 0 now]; synchronises"""
+        out = (C.c_longlong * 5)()
+        self._check(self.lib.mvs_propagate_report(self.h, out))
+        return list(out)
 
     # ---- resolution pyramid (include/mvs.h, DESIGN.md section 20) --------------------------------
     def pyramid_downsample_device(self, src_ptr, dst_ptr, nframes=1):
