@@ -77,9 +77,14 @@ int mvs_mix_background(mvs_ctx *ctx, const uint8_t *img_hw3, const uint8_t *bg_h
                        uint8_t *out_hw);
 /* compare, util.cpp:332-361: multi-scale L1 pyramid difference, out_hw = H*W float */
 int mvs_compare(mvs_ctx *ctx, const uint8_t *prev_hw, const uint8_t *next_hw, float *out_hw);
-/* flowRemap, util.cpp:390-403: bicubic remap by flow (flow_stride floats per pixel, first two used) */
+/* flowRemap, util.cpp:390-403: bicubic remap by flow (flow_stride floats per pixel, first two used).  The sample position (x + u, y + v) is
+ * taken in 1/32 pixel, rounded half to even; samples outside the frame read the constant border, 0.  A coordinate whose x32 value is NaN,
+ * infinite or outside int32 reads the border too -- the pixel's output is 0 -- as the reference's x86 build does (cvRound gives INT_MIN). */
 int mvs_flow_remap(mvs_ctx *ctx, const float *flow, int flow_stride, const uint8_t *image_hw, uint8_t *out_hw);
-/* calculateFlow, flow.cpp:19-42: out_hw4 = H*W*4 float (u, v, variance, 0) */
+/* calculateFlow, flow.cpp:19-42: out_hw4 = H*W*4 float (u, v, variance, 0).  With use_farneback the window is (H + W) / 100 (flow.cpp:24),
+ * which is 0 below H + W = 100 (the reference divides by its square there and returns NaN everywhere): such a call is refused with
+ * MVS_EINVAL and a message that names the window, before anything is queued -- by mvs_flow, mvs_process_frame and mvs_process_frame_slots
+ * alike.  The variational form (use_farneback = 0) has no window and is valid for every context size, 2 x 2 included. */
 int mvs_flow(mvs_ctx *ctx, const uint8_t *prev_hw, const uint8_t *next_hw, int use_farneback, float *out_hw4);
 
 /* ---- per-pixel triangulation + normals: replaces triangulatePixels (util.cpp:167-329, recon.cpp:114) -------------- */

@@ -1467,6 +1467,7 @@ int flow_farneback_batch_device(mvs_ctx *ctx, const uint8_t *prev_dev, const uin
     const size_t P = (size_t)ctx->W * ctx->H;
     if (B < 1 || B > 64) return fail(ctx, MVS_EINVAL, "flow batch of %d", B);
     int rc;
+    if ((rc = flow_check_window(ctx, 1, "flow batch"))) return rc;
     const FlowBatchBufs probe = flow_batch_layout(nullptr, P, B);
     if ((rc = ensure(ctx, ctx->flow_batch_arena, sizeof(float) * probe.floats + 256))) return rc;
     if ((rc = ensure_cubic_table(ctx))) return rc;
@@ -1476,13 +1477,21 @@ int flow_farneback_batch_device(mvs_ctx *ctx, const uint8_t *prev_dev, const uin
     return farneback_batch_enqueue(ctx, prev_dev, next_dev, B, out4_dev, b);
 }
 
+int flow_check_window(mvs_ctx *ctx, int use_farneback, const char *who)
+{
+    if (use_farneback && ctx->W + ctx->H < 100)
+        return fail(ctx, MVS_EINVAL, "%s: the Farneback window (H + W) / 100 is 0 at %d x %d (H + W >= 100 needed; the variational form has no window)", who, ctx->W, ctx->H);
+    return MVS_OK;
+}
+
 // calculateFlow on device buffers (prev/next: H*W u8, out4: H*W*4 f32), all in-stream
 int flow_device(mvs_ctx *ctx, const uint8_t *prev_dev, const uint8_t *next_dev, int use_farneback, float *out4_dev)
 {
     const size_t P = (size_t)ctx->W * ctx->H;
     FlowBufs b;
-    int rc = flow_prepare(ctx, b, use_farneback);
+    int rc = flow_check_window(ctx, use_farneback, "flow");
     if (rc) return rc;
+    if ((rc = flow_prepare(ctx, b, use_farneback))) return rc;
     // the caller's device buffers ARE the inputs and the output (round 6: three device-to-device copies per flow fewer -- each a launch of its own
     // with ~10 us of host latency, per side view of every main frame); the arena's own p8 / n8 / out4 serve mvs_flow's host buffers
     (void)P;
@@ -1497,8 +1506,9 @@ int flow_device(mvs_ctx *ctx, const uint8_t *prev_dev, const uint8_t *next_dev, 
 int flow_only_device(mvs_ctx *ctx, const uint8_t *prev_dev, const uint8_t *next_dev, int use_farneback, float *flow2_dev)
 {
     FlowBufs b;
-    int rc = flow_prepare(ctx, b, use_farneback, true);
+    int rc = flow_check_window(ctx, use_farneback, "flow");
     if (rc) return rc;
+    if ((rc = flow_prepare(ctx, b, use_farneback, true))) return rc;
     b.p8 = const_cast<uint8_t *>(prev_dev);
     b.n8 = const_cast<uint8_t *>(next_dev);
     b.flow2 = flow2_dev;
@@ -1528,6 +1538,7 @@ extern "C" {
 int mvs_flow(mvs_ctx *ctx, const uint8_t *prev_hw, const uint8_t *next_hw, int use_farneback, float *out_hw4)
 {
     if (!ctx || !prev_hw || !next_hw || !out_hw4) return fail(ctx, MVS_EINVAL, "mvs_flow: null argument");
+    if (flow_check_window(ctx, use_farneback, "mvs_flow")) return MVS_EINVAL;
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)ctx->W * ctx->H;
     FlowBufs b;

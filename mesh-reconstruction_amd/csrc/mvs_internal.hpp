@@ -332,6 +332,9 @@ int projected_side_pass(mvs_ctx *ctx, const uint8_t *frame_dev, const float proj
                         float *mix_depth = nullptr, uint8_t *mix_out = nullptr);   // ... and the half that does
 int projected_prepare_views(mvs_ctx *ctx, const uint8_t *const *frames_dev, int nframes);   // the frame textures (wrap padding + mip chain) of nframes (<= 32) side frames, a device pointer each, per launch
 int mix_background_device(mvs_ctx *ctx, const uint8_t *img3_dev, const uint8_t *bg_dev, float *depth_dev, uint8_t *out_dev);
+// calculateFlow's Farneback window is (H + W) / 100 (flow.cpp:24): 0 below H + W = 100, where the box scale 1 / window^2 is infinite and every flow NaN.
+// MVS_EINVAL with a message that names the window; checked by every entry point before it queues anything.  The variational form has no window.
+int flow_check_window(mvs_ctx *ctx, int use_farneback, const char *who);
 int flow_device(mvs_ctx *ctx, const uint8_t *prev_dev, const uint8_t *next_dev, int use_farneback, float *out4_dev);
 int flow_only_device(mvs_ctx *ctx, const uint8_t *prev_dev, const uint8_t *next_dev, int use_farneback, float *flow2_dev);  // without the variance channel ...
 int flow_variance_batch_device(mvs_ctx *ctx, const uint8_t *prev8, const uint8_t *next8, const float *flow2, int B, uint8_t *r8, float *var, float *out4);  // ... which this adds for B flows per launch

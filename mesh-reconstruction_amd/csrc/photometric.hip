@@ -183,7 +183,14 @@ __global__ __launch_bounds__(256) void remap_cubic_kernel(const float *__restric
     out += img_z * blockIdx.z;
     const float *f = flow + ((size_t)y * W + x) * stride;
     const float mx = f[0] + (float)x, my = f[1] + (float)y;
-    const int qx = __float2int_rn(mx * 32.0f), qy = __float2int_rn(my * 32.0f);
+    const float mx32 = mx * 32.0f, my32 = my * 32.0f;
+    // cvRound gives INT_MIN for what is no number or no int32 (the reference's x86 build): far outside the frame, the constant border.
+    // (__float2int_rn would give 0 for NaN -- pixel (0, 0) -- and saturate the infinities.)
+    if (!(mx32 >= -2147483648.0f && mx32 < 2147483648.0f) || !(my32 >= -2147483648.0f && my32 < 2147483648.0f)) {
+        out[(size_t)y * W + x] = 0;
+        return;
+    }
+    const int qx = __float2int_rn(mx32), qy = __float2int_rn(my32);
     int sx = (qx >> 5) - 1, sy = (qy >> 5) - 1;
     const int fx = qx & 31, fy = qy & 31;
     sx = max(-32767, min(32767, sx));

@@ -116,6 +116,7 @@ static int process_frame_impl(mvs_ctx *ctx, const float main_cam[16], const uint
 {
     const bool slots = !main_frame_hw;
     if (nside > 32) return fail(ctx, MVS_EINVAL, "mvs_process_frame: at most 32 side views");
+    if (flow_check_window(ctx, use_farneback, slots ? "mvs_process_frame_slots" : "mvs_process_frame")) return MVS_EINVAL;   // before anything is queued
     if (!ctx->soup.ptr) return fail(ctx, MVS_ESTATE, "mvs_process_frame: no mesh loaded (mvs_load_mesh)");
     if (slots) {
         for (int i = -1; i < nside; i++) {

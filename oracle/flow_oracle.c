@@ -460,7 +460,7 @@ static void warp_linear_q5(const float *img, int W, int H, const float *u, const
         for (int x = 0; x < W; x++) {
             const size_t p = (size_t)y * W + x;
             const float mx = (float)x + u[p], my = (float)y + v[p];
-            const int qx = (int)lrintf(mx * 32.0f), qy = (int)lrintf(my * 32.0f);
+            const int qx = orc_cvround_q5(mx * 32.0f), qy = orc_cvround_q5(my * 32.0f);  /* (INT_MIN when not a number or beyond int32) */
             const int sx = qx >> 5, sy = qy >> 5;
             const float fx = (float)(qx & 31) * (1.0f / 32), fy = (float)(qy & 31) * (1.0f / 32);
             const float w0 = (1.f - fy) * (1.f - fx), w1 = (1.f - fy) * fx, w2 = fy * (1.f - fx), w3 = fy * fx;

@@ -25,6 +25,18 @@ extern "C" {
 
 #define ORC_BACKGROUND_DEPTH 1.0f /* recon.hpp:30 */
 
+/* cvRound(v) of a 1/32-pixel map coordinate as the reference's x86 build computes it (cvtss2si): round half to even, and the "integer
+ * indefinite" INT_MIN for NaN, +-infinity and anything outside int32 -- never the wrap of a 64-bit lrintf cast to int.  INT_MIN >> 5 lies
+ * far left of / above every frame: flowRemap's constant border (0) there, the replicated edge pixel in the variational warp. */
+#ifndef __cplusplus
+#include <math.h>
+static inline int orc_cvround_q5(float v)
+{
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return (int)(-2147483647 - 1);
+    return (int)lrintf(v);
+}
+#endif
+
 /* ---- plane-sweep cost volume (D-plane generalisation of shader.frag:11-25) ------------------- */
 
 /* 3x4 "view matrix" Q = S * side_cam * inverse(main_cam) rounded to f32 (row-major, 12 floats):

@@ -234,8 +234,9 @@ void orc_flow_remap(const float *flow, int stride, const uint8_t *image, int W, 
             const float *f = flow + ((size_t)y * W + x) * stride;
             /* util.cpp:395-398: absolute map = flow + (x, y), in f32 */
             const float mx = f[0] + (float)x, my = f[1] + (float)y;
-            /* convertMaps: cvRound(m * 32) (round half to even), then split into integer and 5-bit fraction */
-            const int qx = (int)lrintf(mx * (float)TAB), qy = (int)lrintf(my * (float)TAB);
+            /* convertMaps: cvRound(m * 32) (round half to even; INT_MIN for NaN, infinities and beyond int32, which lands in the
+             * border: output 0), then split into integer and 5-bit fraction */
+            const int qx = orc_cvround_q5(mx * (float)TAB), qy = orc_cvround_q5(my * (float)TAB);
             int sx = (qx >> 5) - 1, sy = (qy >> 5) - 1;
             /* coordinates are carried as short in OpenCV's fixed-point maps */
             const int fx = qx & (TAB - 1), fy = qy & (TAB - 1);

@@ -254,6 +254,8 @@ class Oracle:
 
     def calculate_flow(self, prev, nxt, use_farneback):
         H, W = prev.shape
+        if use_farneback and H + W < 100:   # the library's MVS_EINVAL: the window (H + W) // 100 is 0 there and the C returns an all-NaN flow
+            raise ValueError("calculate_flow: the Farneback window (H + W) // 100 is 0 at %d x %d" % (W, H))
         a, b = np.ascontiguousarray(prev, np.uint8), np.ascontiguousarray(nxt, np.uint8)
         out = np.empty((H, W, 4), np.float32)
         f = self.lib.orc_calculate_flow
