@@ -98,12 +98,21 @@ __global__ void splat_kernel(Grid g, const float *__restrict__ pts, const float 
 // a uniform grid (cell ~ two sample spacings of a surface sampling: a handful of samples per cell), a sample scans the block of
 // (2R + 1)^3 cells around its own -- one binary search per cell row, the cells of a row are consecutive keys -- and stops as soon as
 // its KNN-th distance is at most R cells: everything outside the block is farther than that.  R doubles otherwise (sparse corners,
-// volumetric clouds).  Exact, not approximate -- up to a budget of KNN_BUDGET candidates per sample, which only a cloud with most of
-// its samples inside one cell (densities many orders of magnitude apart) can exhaust: the distances found until then are used (an upper
-// bound of the true ones), so that no input can turn the search into an n^2 scan that runs for minutes.  The host sums the per-sample
-// means in sample order (deterministic).
+// volumetric clouds), and a later pass scans only the SHELL of cells the previous block did not cover: the list of the nearest
+// distances is kept from pass to pass and never sees a sample twice.  The contract:
+//   - a sample's value is the exact one unless its budget of KNN_BUDGET candidates (a probed cell row is charged KNN_ROW_COST) is
+//     spent, which only a cloud with most of its samples inside one cell (densities many orders of magnitude apart) or a sample tens
+//     of cells from every other can do -- no input can turn the search into an n^2 scan that runs for minutes;
+//   - when the budget is spent the scan stops where it is and the value is computed from the true distances to min(KNN, n - 1)
+//     DISTINCT OTHER samples found until then, whichever pass found them: never below the exact value, and never 0 for a sample that
+//     has a non-coincident neighbour;
+//   - a sample that holds fewer than min(KNN, n - 1) neighbours at that point (it is isolated by tens of empty cells: a far outlier,
+//     a homogeneous w near 0) finishes with one linear scan of the sorted array, which is exact.  Such samples sit alone in blocks of
+//     65^3 cells at the least, so a cloud holds few of them;
+//   - the value does not depend on the order of the threads or of the scan (the list is the sorted KNN smallest of a set).
+// The host sums the per-sample means in sample order (deterministic).
 constexpr int KNN_BUDGET = 1 << 17;
-constexpr int KNN_ROW_COST = 16;  // what a probed cell row is charged, in candidates (two ~20-step binary searches)
+constexpr int KNN_ROW_COST = 16;  // what a probed cell row is charged, in candidates (its searches in the sorted keys)
 struct CellGrid {
     float ox, oy, oz, inv, cell;
     int nx, ny, nz;
@@ -146,6 +155,38 @@ __device__ __forceinline__ int lower_bound_u32(const unsigned *__restrict__ a, i
     return lo;
 }
 
+// the lower bound of `key` in a[from .. n), where everything before `from` is below `key`: gallops from `from` (the cells of a row are
+// neighbours in the sorted array: a few steps instead of a search over all n)
+__device__ __forceinline__ int lower_bound_from(const unsigned *__restrict__ a, int n, int from, unsigned key)
+{
+    int lo = from, hi = from, step = 1;
+    while (hi < n && a[hi] < key) {
+        lo = hi + 1;
+        hi += step;
+        step *= 2;
+    }
+    hi = min(hi, n);
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void knn_insert(float (&best)[KNN], const float4 &p, const float4 &q)
+{
+    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+    float d = dx * dx + dy * dy + dz * dz;
+    if (d < best[KNN - 1]) {  // insertion into the ascending list
+#pragma unroll
+        for (int u = 0; u < KNN; u++) {
+            const float lo = fminf(best[u], d);
+            d = fmaxf(best[u], d);
+            best[u] = lo;
+        }
+    }
+}
+
 __global__ void knn_spacing_kernel(CellGrid c, const unsigned *__restrict__ keys, const float4 *__restrict__ sorted, const int *__restrict__ ids, int n,
                                    float *__restrict__ out)
 {
@@ -155,40 +196,48 @@ __global__ void knn_spacing_kernel(CellGrid c, const unsigned *__restrict__ keys
     int ci, cj, ck;
     cell_of(c, p.x, p.y, p.z, ci, cj, ck);
     float best[KNN];
+#pragma unroll
+    for (int t = 0; t < KNN; t++) best[t] = 3.0e38f;
     const int rmax = max(c.nx, max(c.ny, c.nz));
     int budget = KNN_BUDGET;
-    for (int R = 1;; R *= 2) {
-#pragma unroll
-        for (int t = 0; t < KNN; t++) best[t] = 3.0e38f;
+    // Rp: the radius of the block the passes before this one covered (-1: none yet); a row that crosses that block is scanned on either side of it
+    for (int R = 1, Rp = -1; budget > 0; Rp = R, R *= 2) {
         const int i0 = max(ci - R, 0), i1 = min(ci + R, c.nx - 1);
-        for (int k = max(ck - R, 0); k <= min(ck + R, c.nz - 1); k++)
-            for (int j = max(cj - R, 0); j <= min(cj + R, c.ny - 1); j++) {
+        for (int k = max(ck - R, 0); k <= min(ck + R, c.nz - 1) && budget > 0; k++)
+            for (int j = max(cj - R, 0); j <= min(cj + R, c.ny - 1) && budget > 0; j++) {  // (budget <= 0: it is spent, the scan stops where it is)
                 const unsigned row = (unsigned)((k * c.ny + j) * c.nx);
+                const bool crosses = abs(k - ck) <= Rp && abs(j - cj) <= Rp;
+                budget -= KNN_ROW_COST;  // a probed row costs its searches even when it is empty (a far outlier --
+                                         // homogeneous w near 0 -- walks (2R + 1)^2 empty rows per doubling of R)
+                if (best[KNN - 1] == 0.0f) continue;  // nothing can come closer than coincident samples
+                // the row's samples are [a, b); [ha, hb) of them lie in the cells of the old block (none: ha = hb = a)
                 const int a = lower_bound_u32(keys, n, row + (unsigned)i0);
-                int b = lower_bound_u32(keys, n, row + (unsigned)i1 + 1u);
-                if (best[KNN - 1] == 0.0f || budget <= 0) b = a;  // nothing can come closer than coincident samples; or the budget is spent
-                budget -= (b - a) + KNN_ROW_COST;  // a probed row costs its two binary searches even when it is empty (a far
-                                                   // outlier -- homogeneous w near 0 -- walks (2R + 1)^2 empty rows per doubling of R)
-                for (int t = a; t < b; t++) {
-                    if (t == s) continue;
-                    const float4 q = sorted[t];
-                    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-                    float d = dx * dx + dy * dy + dz * dz;
-                    if (d < best[KNN - 1]) {  // insertion into the ascending list
-#pragma unroll
-                        for (int u = 0; u < KNN; u++) {
-                            const float lo = fminf(best[u], d);
-                            d = fmaxf(best[u], d);
-                            best[u] = lo;
-                        }
-                    }
+                int ha = a, hb = a;
+                if (crosses) {
+                    ha = lower_bound_from(keys, n, a, row + (unsigned)max(ci - Rp, i0));
+                    hb = lower_bound_from(keys, n, ha, row + (unsigned)min(ci + Rp, i1) + 1u);
                 }
+                const int b = lower_bound_from(keys, n, hb, row + (unsigned)i1 + 1u);
+                budget -= (ha - a) + (b - hb);
+                for (int t = a; t < ha; t++)
+                    if (t != s) knn_insert(best, p, sorted[t]);
+                for (int t = hb; t < b; t++)
+                    if (t != s) knn_insert(best, p, sorted[t]);
             }
         const float reach = (float)R * c.cell;
-        if (best[KNN - 1] <= reach * reach || R >= rmax || budget <= 0) break;
+        if (best[KNN - 1] <= reach * reach || R >= rmax) break;
+    }
+    int m = 0;
+#pragma unroll
+    for (int t = 0; t < KNN; t++) m += best[t] < 3.0e38f ? 1 : 0;
+    if (m < min(KNN, n - 1)) {  // the budget went on empty rows (a pass that reaches R >= rmax has seen every sample): one linear scan, exact
+#pragma unroll
+        for (int t = 0; t < KNN; t++) best[t] = 3.0e38f;
+        for (int t = 0; t < n; t++)
+            if (t != s) knn_insert(best, p, sorted[t]);
     }
     float sum = 0.0f;
-    int m = 0;
+    m = 0;
 #pragma unroll
     for (int t = 0; t < KNN; t++)
         if (best[t] < 3.0e38f) {
@@ -542,6 +591,92 @@ bool ensure_plans(int G, const char **why)
     return true;
 }
 
+// the samples' bounding box (points: xyzw rows, w divides); false: a coordinate is not finite
+bool bounding_box(const float *points, int n, double lo[3], double hi[3])
+{
+    for (int c = 0; c < 3; c++) lo[c] = 1e300, hi[c] = -1e300;
+    for (int s = 0; s < n; s++) {
+        const float w = points[4 * s + 3];
+        for (int c = 0; c < 3; c++) {
+            const double v = (double)(points[4 * s + c] / w);
+            if (!(v == v) || std::fabs(v) > 1e30) return false;
+            lo[c] = std::min(lo[c], v), hi[c] = std::max(hi[c], v);
+        }
+    }
+    return true;
+}
+
+// step 0 of the header: per sample the mean distance to its KNN nearest other samples (cell grid, sort, search) into per_sample[n], in
+// sample order.  points: the host rows, d_pts: their copy on the device, lo / hi: bounding_box's.  Synchronises `st`.
+// Returns MVS_OK, MVS_ENOMEM (a host vector) or MVS_EHIP.
+int sample_spacings(const float *points, const float *d_pts, int n, const double lo[3], const double hi[3], hipStream_t st, std::vector<float> &per_sample)
+{
+    // The cell grid spans a ROBUST extent of the samples (2nd .. 98th percentile per axis, plus a margin): a few outliers must not
+    // blow the cells up until the real samples share one of them (the search stays exact either way: samples outside the grid are
+    // binned into its border cells, and a border cell is only skipped when it is farther away than the search radius).
+    CellGrid cg;
+    double rlo[3], rhi[3], rside = 0.0, side = 0.0;
+    for (int c = 0; c < 3; c++) side = std::max(side, hi[c] - lo[c]);
+    try {
+        std::vector<float> axis((size_t)n);
+        for (int c = 0; c < 3; c++) {
+            for (int s = 0; s < n; s++) axis[(size_t)s] = points[4 * s + c] / points[4 * s + 3];
+            const size_t a = (size_t)(0.02 * (double)(n - 1)), b = (size_t)(0.98 * (double)(n - 1));
+            std::nth_element(axis.begin(), axis.begin() + (std::ptrdiff_t)a, axis.end());
+            rlo[c] = (double)axis[a];
+            std::nth_element(axis.begin(), axis.begin() + (std::ptrdiff_t)b, axis.end());
+            rhi[c] = (double)axis[b];
+            rside = std::max(rside, rhi[c] - rlo[c]);
+        }
+        per_sample.resize((size_t)n);
+    } catch (...) {
+        return MVS_ENOMEM;
+    }
+    if (!(rside > 0.0)) {  // degenerate percentiles (most samples coincide): the full box
+        rside = side;
+        for (int c = 0; c < 3; c++) rlo[c] = lo[c], rhi[c] = hi[c];
+    }
+    const double cell = std::max(2.0 * rside / std::sqrt((double)n), rside / 1000.0);  // ~ two spacings of a surface sampling; at most ~1000 cells per axis
+    cg.cell = (float)cell;
+    cg.inv = (float)(1.0 / cell);
+    cg.ox = (float)(rlo[0] - 2.0 * cell), cg.oy = (float)(rlo[1] - 2.0 * cell), cg.oz = (float)(rlo[2] - 2.0 * cell);
+    cg.nx = std::max(1, std::min(1024, (int)std::floor((rhi[0] - rlo[0]) / cell) + 5));
+    cg.ny = std::max(1, std::min(1024, (int)std::floor((rhi[1] - rlo[1]) / cell) + 5));
+    cg.nz = std::max(1, std::min(1024, (int)std::floor((rhi[2] - rlo[2]) / cell) + 5));
+    DevBuf k0, k1, i0, i1, sorted, per;
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+    bool ok = k0.alloc((size_t)n * 4) && k1.alloc((size_t)n * 4) && i0.alloc((size_t)n * 4) && i1.alloc((size_t)n * 4) && sorted.alloc((size_t)n * 16) && per.alloc((size_t)n * 4);
+    if (ok) {
+        cell_keys_kernel<<<(n + 255) / 256, 256, 0, st>>>(cg, d_pts, n, k0.as<unsigned>(), i0.as<int>());
+        ok = sort_pairs(k0.as<unsigned>(), k1.as<unsigned>(), i0.as<int>(), i1.as<int>(), (size_t)n, st, &tmp, tmp_bytes);
+    }
+    if (ok) {
+        cell_points_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_pts, i1.as<int>(), n, sorted.as<float4>());
+        knn_spacing_kernel<<<(n + 127) / 128, 128, 0, st>>>(cg, k1.as<unsigned>(), sorted.as<float4>(), i1.as<int>(), n, per.as<float>());
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(per_sample.data(), per.p, (size_t)n * 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (tmp) (void)hipFree(tmp);
+    return ok ? MVS_OK : MVS_EHIP;
+}
+
+// step 4a of the header on the stream: seed from the weight field, then one max-filter pass per axis.  m0, m1: G^3 bytes each; the mask ends in m1.
+void launch_support_mask(const Grid &g, const fix_t *wt, unsigned char *m0, unsigned char *m1, int R, hipStream_t st)
+{
+    const size_t N3 = (size_t)g.G * g.G * g.G;
+    support_seed_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(wt, m0, N3);
+    support_dilate_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(g, m0, m1, R, 0);
+    support_dilate_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(g, m1, m0, R, 1);
+    support_dilate_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(g, m0, m1, R, 2);
+}
+
+// a stream of its own (not the legacy default stream, which synchronises with every blocking stream of the process)
+struct OwnStream {
+    hipStream_t s = nullptr;
+    ~OwnStream() { if (s) (void)hipStreamDestroy(s); }
+    bool create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess; }
+};
+
 }  // namespace
 
 // step 4 of the header: surface nets over a device field (surface_internal.hpp).  Shared with csrc/tsdf.hip (mvs_tsdf_surface).
@@ -607,6 +742,82 @@ extern "C" int mvs_test_cell_patch_table(uint32_t out[256])
     return MVS_OK;
 }
 
+// test hooks (not in mvs.h; tests/meshing_common.py, tests/test_poisson_cases_gpu.py).  Host pointers in and out; each runs on a stream of its
+// own and frees what it allocates.
+// step 0 alone: the n per-sample values behind mvs_surface_spacing's average (points: n xyzw rows)
+extern "C" int mvs_test_average_spacing(const float *points, int n, float *per_sample_out)
+{
+    if (!points || n < 2 || !per_sample_out) return fail(MVS_EINVAL, "mvs_test_average_spacing: bad argument");
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) return fail(MVS_EHIP, "mvs_test_average_spacing: no HIP device");
+    double lo[3], hi[3];
+    if (!bounding_box(points, n, lo, hi)) return fail(MVS_EINVAL, "mvs_test_average_spacing: a point is not finite");
+    if (!(std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2])) > 0.0)) return fail(MVS_EINVAL, "mvs_test_average_spacing: the points have no extent");
+    OwnStream own;
+    if (!own.create()) return fail(MVS_EHIP, "mvs_test_average_spacing: hipStreamCreate failed");
+    DevBuf d_pts;
+    if (!d_pts.alloc((size_t)n * 16)) return fail(MVS_ENOMEM, "mvs_test_average_spacing: device allocation failed");
+    if (hipMemcpy(d_pts.p, points, (size_t)n * 16, hipMemcpyHostToDevice) != hipSuccess) return fail(MVS_EHIP, "mvs_test_average_spacing: upload failed");
+    std::vector<float> per_sample;
+    const int rc = sample_spacings(points, d_pts.as<float>(), n, lo, hi, own.s, per_sample);
+    if (rc != MVS_OK) return fail(rc, "mvs_test_average_spacing: average spacing failed");
+    std::memcpy(per_sample_out, per_sample.data(), (size_t)n * 4);
+    return MVS_OK;
+}
+
+// step 4 alone: the surface nets of a given field (chi: G^3 floats in the node order (k G + j) G + i, support: G^3 bytes or null); the handle
+// answers mvs_surface_counts / mvs_surface_fetch / mvs_surface_grid (no chi, no splat) and is released by mvs_surface_free
+extern "C" int mvs_test_surface_nets(const float *chi, int G, const float *origin3, float h, float iso, const unsigned char *support, mvs_surface **out)
+{
+    if (!chi || G < 2 || G > 512 || !origin3 || !(h > 0.0f) || !out) return fail(MVS_EINVAL, "mvs_test_surface_nets: bad argument");
+    *out = nullptr;
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) return fail(MVS_EHIP, "mvs_test_surface_nets: no HIP device");
+    Grid g;
+    g.G = G, g.ox = origin3[0], g.oy = origin3[1], g.oz = origin3[2], g.h = h;
+    const size_t N3 = (size_t)G * G * G;
+    OwnStream own;
+    if (!own.create()) return fail(MVS_EHIP, "mvs_test_surface_nets: hipStreamCreate failed");
+    DevBuf d_chi, d_mask;
+    if (!d_chi.alloc(N3 * 4) || (support && !d_mask.alloc(N3))) return fail(MVS_ENOMEM, "mvs_test_surface_nets: device allocation failed");
+    if (hipMemcpy(d_chi.p, chi, N3 * 4, hipMemcpyHostToDevice) != hipSuccess || (support && hipMemcpy(d_mask.p, support, N3, hipMemcpyHostToDevice) != hipSuccess))
+        return fail(MVS_EHIP, "mvs_test_surface_nets: upload failed");
+    mvs_surface *res = new (std::nothrow) mvs_surface;
+    if (!res) return fail(MVS_ENOMEM, "mvs_test_surface_nets: host allocation failed");
+    res->grid = g;
+    res->iso = iso;
+    std::string why;
+    const int rc = surface_nets_device(g, d_chi.as<float>(), iso, support ? d_mask.as<unsigned char>() : nullptr, own.s, res, "mvs_test_surface_nets", why);
+    if (rc != MVS_OK) {
+        delete res;
+        g_poisson_error = why;
+        return rc;
+    }
+    *out = res;
+    return MVS_OK;
+}
+
+// step 4a alone: the node mask (G^3 bytes) of a given weight field (G^3 int64) dilated by R nodes
+extern "C" int mvs_test_support_mask(const int64_t *weights, int G, int R, unsigned char *mask_out)
+{
+    if (!weights || G < 2 || G > 512 || R < 0 || !mask_out) return fail(MVS_EINVAL, "mvs_test_support_mask: bad argument");
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) return fail(MVS_EHIP, "mvs_test_support_mask: no HIP device");
+    Grid g;
+    g.G = G, g.ox = g.oy = g.oz = 0.0f, g.h = 1.0f;
+    const size_t N3 = (size_t)G * G * G;
+    OwnStream own;
+    if (!own.create()) return fail(MVS_EHIP, "mvs_test_support_mask: hipStreamCreate failed");
+    DevBuf d_wt, d_mask;
+    if (!d_wt.alloc(N3 * sizeof(fix_t)) || !d_mask.alloc(2 * N3)) return fail(MVS_ENOMEM, "mvs_test_support_mask: device allocation failed");
+    if (hipMemcpy(d_wt.p, weights, N3 * sizeof(fix_t), hipMemcpyHostToDevice) != hipSuccess) return fail(MVS_EHIP, "mvs_test_support_mask: upload failed");
+    unsigned char *m0 = d_mask.as<unsigned char>(), *m1 = m0 + N3;
+    launch_support_mask(g, d_wt.as<fix_t>(), m0, m1, R, own.s);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(mask_out, m1, N3, hipMemcpyDeviceToHost, own.s) != hipSuccess || hipStreamSynchronize(own.s) != hipSuccess)
+        return fail(MVS_EHIP, "mvs_test_support_mask: a kernel failed");
+    return MVS_OK;
+}
+
 extern "C" int mvs_poisson_warmup(int grid_log2)
 {
     if (grid_log2 < 5 || grid_log2 > 9) {
@@ -643,26 +854,15 @@ extern "C" int mvs_poisson_surface_ex(const float *points, const float *normals,
     int devices = 0;
     if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) return fail(MVS_EHIP, "mvs_poisson_surface: no HIP device (this library has no CPU path)");
     // the box: the samples' bounding cube, padded by a quarter of its side on every face (periodic solve: keep the wrap-around away)
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (int s = 0; s < n; s++) {
-        const float w = points[4 * s + 3];
-        for (int c = 0; c < 3; c++) {
-            const double v = (double)(points[4 * s + c] / w);
-            if (!(v == v) || std::fabs(v) > 1e30) return fail(MVS_EINVAL, "mvs_poisson_surface: a point is not finite");
-            lo[c] = std::min(lo[c], v), hi[c] = std::max(hi[c], v);
-        }
-    }
+    double lo[3], hi[3];
+    if (!bounding_box(points, n, lo, hi)) return fail(MVS_EINVAL, "mvs_poisson_surface: a point is not finite");
     double side = 0.0;
     for (int c = 0; c < 3; c++) side = std::max(side, hi[c] - lo[c]);
     if (!(side > 0.0)) return fail(MVS_EINVAL, "mvs_poisson_surface: the points have no extent");
     const double box = 1.5 * side;
     // ---- step 0: the samples' average spacing (device), then the grid ----
-    // a stream of its own (not the legacy default stream, which synchronises with every blocking stream of the process)
-    struct OwnStream {
-        hipStream_t s = nullptr;
-        ~OwnStream() { if (s) (void)hipStreamDestroy(s); }
-    } own;
-    if (hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking) != hipSuccess) return fail(MVS_EHIP, "mvs_poisson_surface: hipStreamCreate failed");
+    OwnStream own;
+    if (!own.create()) return fail(MVS_EHIP, "mvs_poisson_surface: hipStreamCreate failed");
     hipStream_t st = own.s;
     DevBuf d_pts, d_nrm;
     if (!d_pts.alloc((size_t)n * 16) || !d_nrm.alloc((size_t)n * 12)) return fail(MVS_ENOMEM, "mvs_poisson_surface: device allocation failed");
@@ -670,58 +870,10 @@ extern "C" int mvs_poisson_surface_ex(const float *points, const float *normals,
         return fail(MVS_EHIP, "mvs_poisson_surface: upload failed");
     double spacing = 0.0;
     {
-        // The cell grid spans a ROBUST extent of the samples (2nd .. 98th percentile per axis, plus a margin): a few outliers must not
-        // blow the cells up until the real samples share one of them (the search stays exact either way: samples outside the grid are
-        // binned into its border cells, and a border cell is only skipped when it is farther away than the search radius).
-        CellGrid cg;
-        double rlo[3], rhi[3], rside = 0.0;
-        try {
-            std::vector<float> axis((size_t)n);
-            for (int c = 0; c < 3; c++) {
-                for (int s = 0; s < n; s++) axis[(size_t)s] = points[4 * s + c] / points[4 * s + 3];
-                const size_t a = (size_t)(0.02 * (double)(n - 1)), b = (size_t)(0.98 * (double)(n - 1));
-                std::nth_element(axis.begin(), axis.begin() + (std::ptrdiff_t)a, axis.end());
-                rlo[c] = (double)axis[a];
-                std::nth_element(axis.begin(), axis.begin() + (std::ptrdiff_t)b, axis.end());
-                rhi[c] = (double)axis[b];
-                rside = std::max(rside, rhi[c] - rlo[c]);
-            }
-        } catch (...) {
-            return fail(MVS_ENOMEM, "mvs_poisson_surface: host allocation failed");
-        }
-        if (!(rside > 0.0)) {  // degenerate percentiles (most samples coincide): the full box
-            rside = side;
-            for (int c = 0; c < 3; c++) rlo[c] = lo[c], rhi[c] = hi[c];
-        }
-        const double cell = std::max(2.0 * rside / std::sqrt((double)n), rside / 1000.0);  // ~ two spacings of a surface sampling; at most ~1000 cells per axis
-        cg.cell = (float)cell;
-        cg.inv = (float)(1.0 / cell);
-        cg.ox = (float)(rlo[0] - 2.0 * cell), cg.oy = (float)(rlo[1] - 2.0 * cell), cg.oz = (float)(rlo[2] - 2.0 * cell);
-        cg.nx = std::max(1, std::min(1024, (int)std::floor((rhi[0] - rlo[0]) / cell) + 5));
-        cg.ny = std::max(1, std::min(1024, (int)std::floor((rhi[1] - rlo[1]) / cell) + 5));
-        cg.nz = std::max(1, std::min(1024, (int)std::floor((rhi[2] - rlo[2]) / cell) + 5));
-        DevBuf k0, k1, i0, i1, sorted, per;
-        void *tmp = nullptr;
-        size_t tmp_bytes = 0;
-        bool ok = k0.alloc((size_t)n * 4) && k1.alloc((size_t)n * 4) && i0.alloc((size_t)n * 4) && i1.alloc((size_t)n * 4) && sorted.alloc((size_t)n * 16) && per.alloc((size_t)n * 4);
-        std::vector<float> host;
-        try {
-            host.resize((size_t)n);
-        } catch (...) {
-            ok = false;
-        }
-        if (ok) {
-            cell_keys_kernel<<<(n + 255) / 256, 256, 0, st>>>(cg, d_pts.as<float>(), n, k0.as<unsigned>(), i0.as<int>());
-            ok = sort_pairs(k0.as<unsigned>(), k1.as<unsigned>(), i0.as<int>(), i1.as<int>(), (size_t)n, st, &tmp, tmp_bytes);
-        }
-        if (ok) {
-            cell_points_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_pts.as<float>(), i1.as<int>(), n, sorted.as<float4>());
-            knn_spacing_kernel<<<(n + 127) / 128, 128, 0, st>>>(cg, k1.as<unsigned>(), sorted.as<float4>(), i1.as<int>(), n, per.as<float>());
-            ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(host.data(), per.p, (size_t)n * 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-        }
-        if (tmp) (void)hipFree(tmp);
-        if (!ok) return fail(MVS_EHIP, "mvs_poisson_surface: average spacing failed");
-        for (int s = 0; s < n; s++) spacing += (double)host[s];
+        std::vector<float> per_sample;
+        const int src = sample_spacings(points, d_pts.as<float>(), n, lo, hi, st, per_sample);
+        if (src != MVS_OK) return fail(src, src == MVS_ENOMEM ? "mvs_poisson_surface: host allocation failed" : "mvs_poisson_surface: average spacing failed");
+        for (int s = 0; s < n; s++) spacing += (double)per_sample[(size_t)s];
         spacing /= (double)n;
     }
     // ---- the normals' scale.  Their LENGTHS are confidences (triangulatePixels multiplies by a pdf, util.cpp:322-327: lengths of 1e-6 .. 1e-4
@@ -815,10 +967,7 @@ extern "C" int mvs_poisson_surface_ex(const float *points, const float *normals,
             res->support_cells = R;
             PS_TRY(d_mask.alloc(2 * N3), MVS_ENOMEM, "mvs_poisson_surface: device allocation failed");
             unsigned char *m0 = d_mask.as<unsigned char>(), *m1 = m0 + N3;
-            support_seed_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(wt, m0, N3);
-            support_dilate_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(g, m0, m1, R, 0);
-            support_dilate_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(g, m1, m0, R, 1);
-            support_dilate_kernel<<<(unsigned)((N3 + 255) / 256), 256, 0, st>>>(g, m0, m1, R, 2);
+            launch_support_mask(g, wt, m0, m1, R, st);
             PS_TRY(hipGetLastError() == hipSuccess, MVS_EHIP, "mvs_poisson_surface: support mask launch failed");
             support = m1;
         }

@@ -108,12 +108,18 @@ def average_spacing(points, k=6):
     """CGAL::compute_average_spacing(points, k) (cgal_poisson.cpp:77): CGAL queries k + 1 neighbours per sample -- the sample itself comes
     first, at distance 0 -- and divides the sum of the distances by the k + 1 points visited (compute_average_spacing.h, as recalled: CGAL
     is not in this image); averaged over the samples; scipy's k-d tree, float64"""
+    return float(average_spacing_per_sample(points, k).mean())
+
+
+def average_spacing_per_sample(points, k=6):
+    """average_spacing before its final mean: per sample the sum of the distances to its min(k, n - 1) nearest other samples over the
+    points visited (those and the sample itself); float64 on the float32 quotients xyz / w"""
     from scipy.spatial import cKDTree
     p = np.asarray(points, np.float32)
     xyz = (p[:, :3] / p[:, 3:4]).astype(np.float64)
     kk = min(k, len(xyz) - 1)
     d, _ = cKDTree(xyz).query(xyz, k=kk + 1)
-    return float((d.sum(1) / (kk + 1)).mean())
+    return d.sum(1) / (kk + 1)
 
 
 def poisson_grid(points, grid_log2):

@@ -110,3 +110,49 @@ def poisson(hip, pts, nrm, grid_log2=0, smooth=1.0, keep=True, support=None):
         out["chi"], out["splat"] = chi, splat
     hip.mvs_surface_free(s)
     return out
+
+
+# ---- test hooks of csrc/poisson.hip (not in mvs.h): single stages on host arrays ----
+def _check(hip, rc):
+    if rc != 0:
+        hip.mvs_surface_last_error.restype = ctypes.c_char_p
+        raise RuntimeError("%d: %s" % (rc, hip.mvs_surface_last_error().decode()))
+
+
+def spacing_per_sample(hip, pts):
+    """step 0 alone: per sample the mean distance to its 6 nearest other samples, as the device search finds it (float32[n])"""
+    pts = np.ascontiguousarray(pts, np.float32)
+    out = np.full(len(pts), np.nan, np.float32)
+    _check(hip, hip.mvs_test_average_spacing(pts.ctypes.data_as(ctypes.c_void_p), len(pts), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def surface_nets(hip, chi, iso, origin, h, support=None):
+    """step 4 alone on a host field chi[z][y][x] (support: node mask or None) -> (vertices V x 4 float32, faces F x 3 int32)"""
+    chi = np.ascontiguousarray(chi, np.float32)
+    G = chi.shape[0]
+    assert chi.shape == (G, G, G)
+    origin = np.ascontiguousarray(origin, np.float32)
+    mask = None if support is None else np.ascontiguousarray(support, np.uint8)
+    assert mask is None or mask.shape == chi.shape
+    s = ctypes.c_void_p()
+    _check(hip, hip.mvs_test_surface_nets(chi.ctypes.data_as(ctypes.c_void_p), G, origin.ctypes.data_as(ctypes.c_void_p), ctypes.c_float(h), ctypes.c_float(iso),
+                                          None if mask is None else mask.ctypes.data_as(ctypes.c_void_p), ctypes.byref(s)))
+    nv, nf = ctypes.c_int(-1), ctypes.c_int(-1)
+    assert hip.mvs_surface_counts(s, ctypes.byref(nv), ctypes.byref(nf)) == 0
+    v = np.zeros((nv.value, 4), np.float32)
+    f = np.zeros((nf.value, 3), np.int32)
+    assert hip.mvs_surface_fetch(s, v.ctypes.data_as(ctypes.c_void_p), f.ctypes.data_as(ctypes.c_void_p)) == 0
+    hip.mvs_surface_free(s)
+    return v, f
+
+
+def support_mask(hip, weights, R):
+    """step 4a alone: weights int64 [z][y][x] -> node mask bool [z][y][x], dilated by R nodes"""
+    w = np.ascontiguousarray(weights, np.int64)
+    G = w.shape[0]
+    assert w.shape == (G, G, G)
+    out = np.full(w.shape, 255, np.uint8)
+    _check(hip, hip.mvs_test_support_mask(w.ctypes.data_as(ctypes.c_void_p), G, int(R), out.ctypes.data_as(ctypes.c_void_p)))
+    assert out.max(initial=0) <= 1
+    return out.astype(bool)
