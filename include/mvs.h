@@ -420,6 +420,24 @@ int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius,
 #define MVS_COST_ZNCC    1   /* rules 1-4 of mvs_sweep_run_zncc */
 #define MVS_KEEP_ALL     0   /* keep: every counted view */
 int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, int radius, int keep, unsigned flags);
+/* mvs_sweep_run_bestk with a guide-gated support window (csrc/bestk_gated.hip; DESIGN.md section 26 is the contract; bit-identical to
+ * tests/gated_mirror.py).  Fixed sampler only.  Beside a depth step the square window of p holds pixels of the other surface; where the
+ * step coincides with an edge of a guide image G, the gate takes them out: G is the H x W u8 image at guide_dev (on the context's GPU,
+ * read during the call's kernel), or the staged main image when guide_dev is NULL.
+ *   Rule 1 of mvs_sweep_run_bestk changes in one place: q is a member of M(p) iff it is inside the frame within the window, ok(q), and
+ *   |G(q) - G(p)| <= tau.  p passes its own gate; the gate depends on neither plane nor view.  Everything else is rules 3-4 of
+ *   mvs_sweep_run_zncc and rules 1-4 of mvs_sweep_run_bestk over that M: the same exact integers, the same one-rounding f32, the same packed
+ *   cell, maps and state afterwards.  A view counts iff ok(p) and, for MVS_COST_ZNCC, va > 0 and vb > 0 over the gated members.
+ * radius is 1..4 for both costs (radius 0 has no window to gate), tau 0..255, keep 1..8 or MVS_KEEP_ALL; MVS_COST_ZNCC with MVS_KEEP_ALL is
+ * the gated ZNCC sweep.  tau = 255, or a constant guide at any tau, writes mvs_sweep_run_bestk's bytes.
+ * WARNING: a tau below the texture's own contrast takes most members out, and ZNCC then has little or no variance left to correlate (a view
+ * whose gated va or vb is 0 does not count): on the occluder scene tau 15 is worse than tau 30 with keep 2.  Choose
+ * tau between the texture's contrast and the contrast across the edges that matter.
+ * The window is not separable, so a pixel reads (2 radius + 1)^2 elements per (plane, view) where mvs_sweep_run_bestk reads about
+ * 2 (2 radius + 1).  Asynchronous on the context's stream, timed under MVS_K_SWEEP; it allocates nothing of its own.
+ * Errors: those of mvs_sweep_run_bestk, and MVS_EINVAL for radius 0 and for tau outside 0..255.  Every check comes before the first
+ * allocation; after an error nothing is written and the context stays usable. */
+int mvs_sweep_run_bestk_gated(mvs_ctx *ctx, int view_first, int view_count, int cost, int radius, int keep, int tau, const void *guide_dev, unsigned flags);
 /* Band sweep with windowed costs: mvs_sweep_run_bestk with plane d of pixel q at prior(q) + delta_d (csrc/band_bestk.hip; DESIGN.md
  * section 24 is the contract; bit-identical to tests/band_bestk_mirror.py).  Fixed sampler only.  It joins the band sweep's planes, spent
  * where a prior says the surface is, with the matching costs that survive exposure drift (ZNCC) and occlusion (best-K), so that the
@@ -574,7 +592,7 @@ int mvs_depth_filter_fetch(mvs_ctx *ctx, float *depth_hw);
  * It propagates the preference of a window across a depth step for the nearer surface as well: beside occluders it does not help and
  * random steps of a coarse plane step make it worse (DESIGN.md section 25 has the figures).
  *   The stage touches no sweep, band, selection or filter state; it reads the staged frames however they got there (host setters,
- * _device forms, frame-store slots).  Its maps -- five H * W maps and the counters -- are allocated by the first mvs_propagate_init; a
+ * _device forms, frame-store slots).  Its maps -- five H * W maps, H * W bytes for a guide (mvs_propagate_set_gate) and the counters -- are allocated by the first mvs_propagate_init; a
  * context that never calls it allocates nothing.  Asynchronous on the context's stream (one launch per half, no host synchronisation),
  * timed under MVS_K_SWEEP.
  * Errors: MVS_EINVAL for a NULL ctx, depth_dev or out, an unknown cost, a radius outside the cost's range, keep outside 0..8, a view
@@ -585,6 +603,16 @@ int mvs_depth_filter_fetch(mvs_ctx *ctx, float *depth_hw);
 #define MVS_PROPAGATE_SLOPES 1u
 int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int view_count, int cost, int radius, int keep, float max_step, unsigned flags);
 int mvs_propagate_run(mvs_ctx *ctx, int iterations, float dz, float dg, int nrandom, unsigned seed);
+/* Guide gate of the propagation's windows.  Rule 1 above gains one clause: member q of p's window is live iff it is
+ * live as stated there AND |G(q) - G(p)| <= tau; everything else stands (candidates, the strict rule 4, the counters, run(a) then run(b)
+ * = run(a + b)).  The call only records (tau, guide_dev) on the context; the default is (255, NULL), with which every call is bit-identical
+ * to an ungated one.  The NEXT mvs_propagate_init takes the recorded gate, and the mvs_propagate_run calls that follow use what that init
+ * took: a set_gate between init and run changes nothing until the next init.  With guide_dev NULL, G is the staged main image; otherwise
+ * init copies H * W bytes from guide_dev (u8, on the context's GPU) on the context's stream into the stage's own allocation, so the
+ * caller's buffer must be valid from this call to the end of that init and not longer.
+ * WARNING, as for mvs_sweep_run_bestk_gated: a tau below the texture's own contrast starves ZNCC of variance.
+ * Errors: MVS_EINVAL for a NULL ctx or tau outside 0..255 (nothing is recorded then). */
+int mvs_propagate_set_gate(mvs_ctx *ctx, int tau, const void *guide_dev);
 int mvs_propagate_fetch(mvs_ctx *ctx, float *z_hw, float *gx_hw, float *gy_hw, unsigned int *cells_hw);
 void *mvs_propagate_depth_device(mvs_ctx *ctx);
 void *mvs_propagate_cost_device(mvs_ctx *ctx);

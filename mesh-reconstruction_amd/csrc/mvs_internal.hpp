@@ -229,6 +229,12 @@ struct mvs_ctx {
     bool prop_have = false;
     int prop_cost = 0, prop_radius = 0, prop_keep = 0, prop_view_first = 0, prop_view_count = 0;
     long long prop_iter = 0;
+    // its guide gate (section 26): what mvs_propagate_set_gate recorded for the next init, and what the last init took -- tau and whether
+    // the guide is the stage's own copy (H*W u8 behind the five maps) or the main image
+    int prop_gate_tau = 255;
+    const void *prop_gate_guide = nullptr;
+    int prop_tau = 255;
+    bool prop_guide_own = false;
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

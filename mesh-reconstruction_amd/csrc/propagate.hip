@@ -17,6 +17,9 @@
 // loop, and the two window loops are NOT unrolled: unrolled, the samples' frame-test masks of a whole window row are live at once and
 // every instantiation with a window spilled 3 to 79 scalar registers (ZNCC at radius 2 took 230 vector registers); as loops none
 // spills and the vector registers stay at 54 to 78.  36 instantiations as in bestk.hip.
+// The guide gate of DESIGN.md section 26 (mvs_propagate_set_gate) is two kernel arguments, not a template parameter: a member is live only
+// if its guide value is within tau of the centre's, read from a second byte tile in LDS (the main image again, or the stage's copy of the
+// caller's guide); tau = 255, the default, passes every member, so an ungated run computes what it computed without the gate.
 #include "bestk_rules.hpp"
 
 #include <cmath>
@@ -39,6 +42,8 @@ struct PropArgs {
     int nrandom;
     float dz, dg;                    // the random steps of this iteration
     uint32_t seed;                   // mix(seed + (2 t + h))
+    int tau;                         // the gate of section 26: member q of p is live only if |G(q) - G(p)| <= tau (255: no gate)
+    const uint8_t *guide;            // G, H*W; null: the main image
 };
 
 __host__ __device__ __forceinline__ uint32_t prop_mix(uint32_t x)
@@ -73,6 +78,7 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
     constexpr bool ZNCC = COST == MVS_COST_ZNCC;
     __shared__ uint32_t lut[1024];
     __shared__ uint8_t mainl[S::SAMPLES];   // [HH][HW] the main image of tile + halo (0 outside the frame: such a member is never sampled)
+    __shared__ uint8_t guidel[S::SAMPLES];  // [HH][HW] the gate's guide likewise: the main image again, or the stage's copy of the caller's
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * ZN_TW, y0 = blockIdx.y * ZN_TH;
 #pragma unroll
@@ -81,7 +87,10 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
         const int hy = i / S::HW, hx = i - hy * S::HW;
         const int col = x0 - R + hx, row = y0 - R + hy;
         const bool in = col >= 0 && col < p.W && row >= 0 && row < p.H;
-        mainl[i] = in ? p.main_img[(size_t)row * p.W + col] : (uint8_t)0;
+        const size_t at = in ? (size_t)row * p.W + col : 0;
+        const uint8_t m = in ? p.main_img[at] : (uint8_t)0;
+        mainl[i] = m;
+        guidel[i] = (in && a.guide) ? a.guide[at] : m;
     }
     __syncthreads();   // the only barrier: everything below is per thread
     const float hix = ZN_MAGIC + 132.0f + 256.0f * (float)p.W, hiy = ZN_MAGIC + 132.0f + 256.0f * (float)p.H;
@@ -97,6 +106,7 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
         float z = a.z[pix], gx = a.gx[pix], gy = a.gy[pix];
         uint32_t cell = init ? 0u : a.cells[pix];
         cls = PR_KEPT;
+        const uint32_t g0 = guidel[(ly + R) * S::HW + lx + R];
         const int ncand = init ? 1 : 8 + a.nrandom;
         for (int ci = 0; ci < ncand; ci++) {
             // the candidate (cz, cgx, cgy); cz = NaN: there is none (such a candidate has no counted view and never wins)
@@ -153,7 +163,9 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
                         const int qc = col + dc;
                         const bool in = qc >= 0 && qc < p.W && qr >= 0 && qr < p.H;
                         const float zq = (cz + cgx * (float)dc) + zr;
-                        const float zs = (in && prop_inside(zq)) ? zq : __builtin_nanf("");   // not live: the sampler's s.w > 0 test rejects NaN
+                        const uint32_t gq = guidel[(ly + dr + R) * S::HW + lx + dc + R];
+                        const bool gate = max(gq, g0) - min(gq, g0) <= (uint32_t)a.tau;
+                        const float zs = (in && gate && prop_inside(zq)) ? zq : __builtin_nanf("");   // not live: the sampler's s.w > 0 test rejects NaN
                         const float xn = __builtin_fmaf((float)(2 * qc + 1), p.invW, -1.0f);
                         const Affine A = view_affine(q, xn, yn);
                         const uint32_t am = mainl[(ly + dr + R) * S::HW + lx + dc + R];
@@ -258,6 +270,8 @@ void pass(mvs_ctx *ctx, PropArgs &a)
     a.cost = maps + 4 * P;
     a.counters = (unsigned long long *)ctx->prop_counters.ptr;
     a.keep = ctx->prop_keep;
+    a.tau = ctx->prop_tau;
+    a.guide = ctx->prop_guide_own ? (const uint8_t *)(maps + 5 * P) : nullptr;
     SweepParams p;
     fill_params(ctx, p, ctx->prop_view_first, ctx->prop_view_count, ZN_TH, ZN_PC);
     if (ctx->prop_cost == MVS_COST_ZNCC)
@@ -299,7 +313,7 @@ int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int 
     if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler addresses images of up to 16383 x 16383", who);
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)ctx->W * ctx->H;
-    if ((rc = ensure(ctx, ctx->prop_maps, 5 * P * sizeof(float)))) return rc;   // z, gx, gy, the cells, the cost map
+    if ((rc = ensure(ctx, ctx->prop_maps, 5 * P * sizeof(float) + P))) return rc;   // z, gx, gy, the cells, the cost map; the gate's guide (u8)
     if ((rc = ensure(ctx, ctx->prop_counters, 4 * sizeof(unsigned long long)))) return rc;
     if ((rc = ensure_fx_lut(ctx))) return rc;
     ctx->prop_cost = cost;
@@ -308,7 +322,10 @@ int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int 
     ctx->prop_view_first = view_first;
     ctx->prop_view_count = view_count;
     ctx->prop_iter = 0;
+    ctx->prop_tau = ctx->prop_gate_tau;
+    ctx->prop_guide_own = ctx->prop_gate_guide != nullptr;
     float *maps = (float *)ctx->prop_maps.ptr;
+    if (ctx->prop_guide_own) MVS_HIP(ctx, hipMemcpyAsync(maps + 5 * P, ctx->prop_gate_guide, P, hipMemcpyDeviceToDevice, ctx->stream));
     MVS_HIP(ctx, hipMemsetAsync(ctx->prop_counters.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
     {
         ProfileScope ps(ctx, MVS_K_SWEEP);
@@ -360,6 +377,15 @@ int mvs_propagate_run(mvs_ctx *ctx, int iterations, float dz, float dg, int nran
     }
     MVS_HIP(ctx, hipGetLastError());
     ctx->prop_iter += iterations;
+    return MVS_OK;
+}
+
+int mvs_propagate_set_gate(mvs_ctx *ctx, int tau, const void *guide_dev)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_propagate_set_gate: null context");
+    if (tau < 0 || tau > 255) return fail(ctx, MVS_EINVAL, "mvs_propagate_set_gate: tau %d outside 0..255", tau);
+    ctx->prop_gate_tau = tau;
+    ctx->prop_gate_guide = guide_dev;
     return MVS_OK;
 }
 

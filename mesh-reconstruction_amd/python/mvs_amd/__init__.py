@@ -144,6 +144,7 @@ ABI = [
     ("mvs_sweep_run_zncc", _i, [_vp, _i, _i, _i, C.c_uint]),
     ("mvs_sweep_run_bestk", _i, [_vp, _i, _i, _i, _i, _i, C.c_uint]),
     ("mvs_sweep_run_band_bestk", _i, [_vp, _i, _i, _vp, _i, _i, _i, C.c_uint]),
+    ("mvs_sweep_run_bestk_gated", _i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.c_uint]),
     ("mvs_pyramid_downsample_device", _i, [_vp, _vp, _vp, _i]),
     ("mvs_pyramid_stage", _i, [_vp, _vp]),
     ("mvs_pyramid_prior", _i, [_vp, _vp, _vp, _i]),
@@ -152,6 +153,7 @@ ABI = [
     ("mvs_depth_filter_fetch", _i, [_vp, _fp]),
     ("mvs_propagate_init", _i, [_vp, _vp, _i, _i, _i, _i, _i, _f, C.c_uint]),
     ("mvs_propagate_run", _i, [_vp, _i, _f, _f, _i, C.c_uint]),
+    ("mvs_propagate_set_gate", _i, [_vp, _i, _vp]),
     ("mvs_propagate_fetch", _i, [_vp, _fp, _fp, _fp, C.POINTER(C.c_uint32)]),
     ("mvs_propagate_depth_device", _vp, [_vp]),
     ("mvs_propagate_cost_device", _vp, [_vp]),
@@ -450,6 +452,9 @@ def _filter_step(ctx, depth_ptr, filter, step, fetch=False):
 
 def _cost_args(cost):
     """the `cost` keyword of the coarse-to-fine helpers: dict(cost="zncc" | "absdiff", radius=, keep=) -> (MVS_COST_*, radius, keep)"""
+    if "tau" in cost:
+        raise ValueError("cost: no key tau: the band level has no guide gate, and a half-gated two-level run would mislead; "
+                         "gate the propagation instead (propagate=dict(..., tau=)) or call Context.sweep_run_bestk_gated")
     unknown = set(cost) - {"cost", "radius", "keep"}
     if unknown:
         raise ValueError("cost: unknown keys %s (cost, radius, keep)" % sorted(unknown))
@@ -463,12 +468,19 @@ def _propagate_step(ctx, depth_ptr, propagate, cost, step, fetch):
     """the `propagate` keyword of the coarse-to-fine helpers: propagate_init + propagate_run on the map at depth_ptr with the windowed cost
     `cost` = (MVS_COST_*, radius, keep); the random steps are dz_steps / dg_steps plane steps `step` of the level that selected the map
     -> the z map (fetch) or None (it stays at propagate_depth_pointer())"""
-    unknown = set(propagate) - {"iterations", "dz_steps", "dg_steps", "nrandom", "seed", "slopes"}
+    unknown = set(propagate) - {"iterations", "dz_steps", "dg_steps", "nrandom", "seed", "slopes", "tau"}
     if unknown:
-        raise ValueError("propagate: unknown keys %s (iterations, dz_steps, dg_steps, nrandom, seed, slopes)" % sorted(unknown))
+        raise ValueError("propagate: unknown keys %s (iterations, dz_steps, dg_steps, nrandom, seed, slopes, tau)" % sorted(unknown))
     if cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
-    ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
+    if "tau" in propagate:      # the guide gate (DESIGN.md section 26), the guide the staged main image; init takes it, so 255 goes back at once
+        ctx.propagate_set_gate(int(propagate["tau"]))
+        try:
+            ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
+        finally:
+            ctx.propagate_set_gate(255)
+    else:
+        ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
     ctx.propagate_run(int(propagate.get("iterations", 3)), float(np.float32(float(propagate.get("dz_steps", 0.5)) * step)),
                       float(np.float32(float(propagate.get("dg_steps", 0.125)) * step)), int(propagate.get("nrandom", 2)), int(propagate.get("seed", 0)))
     return ctx.propagate_fetch()[0] if fetch else None
@@ -495,7 +507,10 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     25; the random steps in plane steps of the band level), and the propagated z map is returned in its place (fetch=False: it stays at
     propagate_depth_pointer()).  It replaces outliers by their neighbours' hypotheses.  WARNING: it does not help beside depth steps: a
     window across a step prefers the nearer surface and propagation spreads that preference (on section 22's occluder scene the bad share
-    of the edge pixels does not fall, and random steps of a coarse plane step raise it)."""
+    of the edge pixels does not fall, and random steps of a coarse plane step raise it).  The optional key tau=0..255 gates the
+    propagation's windows on the staged main image (Context.propagate_set_gate before the init, 255 restored after it; DESIGN.md section
+    26): the gated propagation does repair the edge pixels of a map an ungated sweep made, wherever the step is an intensity edge.
+    cost=dict(..., tau=) raises ValueError: the band level has no gate."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     if propagate is not None and cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
@@ -547,7 +562,8 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
     propagate: None (the calls above), or dict(iterations=, dz_steps=, dg_steps=, nrandom=, seed=, slopes=) as in coarse_to_fine, which
     needs cost=: the finest level's final map becomes the start of ctxs[0].propagate_init / propagate_run and the propagated z map is
     returned in its place (fetch=False: it stays at ctxs[0].propagate_depth_pointer()).  WARNING, as there: propagation does not help
-    beside depth steps, where a window prefers the nearer surface; it spreads that preference."""
+    beside depth steps, where a window prefers the nearer surface; it spreads that preference -- unless it is gated with the optional
+    key tau=, as there."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     if propagate is not None and cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
@@ -1302,6 +1318,17 @@ class Context:
             view_count = self.V - view_first
         self._check(self.lib.mvs_sweep_run_bestk(self.h, int(view_first), int(view_count), int(cost), int(radius), int(keep), int(flags)))
 
+    def sweep_run_bestk_gated(self, cost, radius=2, keep=2, tau=30, guide_ptr=None, view_first=0, view_count=None, flags=MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN):
+        """mvs_sweep_run_bestk_gated: sweep_run_bestk whose window of pixel p holds only the pixels q with |G(q) - G(p)| <= tau (0..255) on
+        the guide G (guide_ptr: device address of H*W uint8, None = the staged main image), so that the pixels across an intensity edge
+        leave the window; radius 1..4 for both costs.  tau 255 or a constant guide gives sweep_run_bestk's bytes.  WARNING: a tau below
+        the texture's own contrast starves ZNCC of variance (views stop counting) and is worse than a larger one.  The window is no
+        longer separable: (2 radius + 1)^2 LDS reads per pixel, plane and view (asynchronous, stream-ordered)"""
+        if view_count is None:
+            view_count = self.V - view_first
+        self._check(self.lib.mvs_sweep_run_bestk_gated(self.h, int(view_first), int(view_count), int(cost), int(radius), int(keep), int(tau),
+                                                       C.c_void_p(int(guide_ptr)) if guide_ptr else None, int(flags)))
+
     def sweep_run_band_bestk(self, prior_ptr, cost, radius=2, keep=MVS_KEEP_ALL, view_first=0, view_count=None, flags=MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN):
         """mvs_sweep_run_band_bestk: sweep_run_bestk with plane d of pixel q at prior(q) + delta_d, delta = the staged plane table
         (sweep_set_planes(D, -hb, +hb)); every window member is sampled at its own prior.  cost MVS_COST_ZNCC (radius 1..4) or
@@ -1348,6 +1375,13 @@ class Context:
             view_count = self.V - view_first
         self._check(self.lib.mvs_propagate_init(self.h, C.c_void_p(int(depth_ptr)) if depth_ptr else None, int(view_first), int(view_count), int(cost), int(radius),
                                                 int(keep), float(max_step), MVS_PROPAGATE_SLOPES if slopes else 0))
+
+    def propagate_set_gate(self, tau, guide_ptr=None):
+        """mvs_propagate_set_gate: records the guide gate the NEXT propagate_init takes (and the propagate_run calls behind it use): window
+        member q of p is live only if |G(q) - G(p)| <= tau (0..255; 255, the default, is no gate) on the guide G (guide_ptr: device
+        address of H*W uint8, copied by that init; None = the staged main image).  The same warning about a small tau as
+        sweep_run_bestk_gated"""
+        self._check(self.lib.mvs_propagate_set_gate(self.h, int(tau), C.c_void_p(int(guide_ptr)) if guide_ptr else None))
 
     def propagate_run(self, iterations, dz, dg, nrandom=2, seed=0):
         """mvs_propagate_run: `iterations` PatchMatch iterations on the hypotheses of propagate_init.  In each of an iteration's two
