@@ -592,7 +592,8 @@ int mvs_depth_filter_fetch(mvs_ctx *ctx, float *depth_hw);
  * It propagates the preference of a window across a depth step for the nearer surface as well: beside occluders it does not help and
  * random steps of a coarse plane step make it worse (DESIGN.md section 25 has the figures).
  *   The stage touches no sweep, band, selection or filter state; it reads the staged frames however they got there (host setters,
- * _device forms, frame-store slots).  Its maps -- five H * W maps, H * W bytes for a guide (mvs_propagate_set_gate) and the counters -- are allocated by the first mvs_propagate_init; a
+ * _device forms, frame-store slots).  Its maps -- five H * W maps, H * W bytes for a guide (mvs_propagate_set_gate), H * W support bytes and a table of 1184 bytes
+ * (mvs_propagate_set_consistency) and the counters -- are allocated by the first mvs_propagate_init; a
  * context that never calls it allocates nothing.  Asynchronous on the context's stream (one launch per half, no host synchronisation),
  * timed under MVS_K_SWEEP.
  * Errors: MVS_EINVAL for a NULL ctx, depth_dev or out, an unknown cost, a radius outside the cost's range, keep outside 0..8, a view
@@ -613,6 +614,40 @@ int mvs_propagate_run(mvs_ctx *ctx, int iterations, float dz, float dg, int nran
  * WARNING, as for mvs_sweep_run_bestk_gated: a tau below the texture's own contrast starves ZNCC of variance.
  * Errors: MVS_EINVAL for a NULL ctx or tau outside 0..255 (nothing is recorded then). */
 int mvs_propagate_set_gate(mvs_ctx *ctx, int tau, const void *guide_dev);
+/* Geometric consistency against stored neighbour depth maps (tests/consistency_mirror.py is the arbiter, bit for
+ * bit).  An opt-in term on the propagation's cells: a hypothesis also pays for disagreeing with what `nslots` (0..8) slots of the depth
+ * store hold, and every pixel knows how many of them confirm what it holds.  The call only records its arguments (the slots are copied;
+ * a slot listed twice counts twice); the default is off (nslots 0, slots may be NULL then), with which every call writes the bytes it
+ * wrote before.  The NEXT mvs_propagate_init takes the recorded term, and the mvs_propagate_run calls that follow use what that init
+ * took.  Everything is f32 with one rounding per operation, as in mvs_fuse_depth.  For the candidate depth cz at pixel p = (row, col):
+ *   1. M is the staged main camera at init, M^-1 made as the depth store makes a slot's inverse; P_j, P_j^-1 are what
+ *      mvs_depth_slot_matrices returns for neighbour j's slot, copied at init.
+ *   2. X = dehomogenised M^-1 (xn(p), yn(p), cz, 1), fusion rule 2.
+ *   3. q = P_j (X, 1); a = q_x / q_w, b = q_y / q_w; u = (a + 1)(W 0.5) - 0.5, v = (1 - b)(H 0.5) - 0.5; the pixel (floorf(v + 0.5),
+ *      floorf(u + 0.5)) is tested against the frame as floats; z_j is the slot's depth there, valid when -1 < z_j < 1.
+ *   4. X_j = the un-projection of (a, b, z_j) through P_j^-1 -- the CONTINUOUS position with the nearest pixel's depth, not the pixel
+ *      centre as in fusion rule 3; s = M (X_j, 1), u_r, v_r as in 3; e = sqrtf(du du + dv dv) with du = u_r - col, dv = v_r - row.
+ *   5. Neighbour j ANSWERS iff q_w > 0, the pixel is in the frame, z_j is valid, s_w > 0 and e <= max_px; e_j = e then, else max_px.
+ *   6. g_j = (uint32)floorf(e_j (weight 255.0f)); g = (sum_j g_j) / nslots in integer division.
+ *   7. A cell c = k << 24 | sum of section 25's rules with k > 0 becomes k << 24 | (sum + k g): its mean cost is the photometric mean
+ *      plus g / 255 grey levels of the cost map's scale (ZNCC: 127.5 (1 - ncc)), and rule 4 there compares these cells.
+ *   8. support(p) = the number of listed neighbours that answer for the hypothesis p HOLDS; 0 for a pixel without one (z not inside
+ *      (-1, 1)) and everywhere when the term is off.  mvs_propagate_support_device is that map (H * W u8, in the stage's allocation; NULL
+ *      before the first init), current after every init and run; mvs_propagate_support_fetch downloads it and synchronises.
+ * The cost map, the report, the candidate list and run(a) then run(b) = run(a + b) stand.  The neighbours' maps are read in the depth
+ * store when the kernel runs, not copied: overwriting a listed slot between init and run is the caller's business (the matrices stay
+ * those of init).  weight 0 leaves z, slopes, cells, cost map and report as without the term and still fills the support map.
+ * WARNING: consistently wrong neighbours confirm each other -- with neighbour maps estimated by the same recipe the gain is small and
+ * can be negative (DESIGN.md section 27 has the figures); the weight is on the cost map's scale.
+ * Errors: at the setter MVS_EINVAL for a NULL ctx, nslots outside 0..8, NULL slots with nslots > 0, a negative slot, a negative or
+ * non-finite weight, a max_px not finite or <= 0, floorf(max_px weight 255) > 1 000 000 (nothing is recorded then).  At init with a term
+ * recorded: MVS_ESTATE without a depth store, for a slot outside it or an unfilled one; MVS_EINVAL for a singular main camera, and for
+ * MVS_KEEP_ALL with so many views that views (65025 + floorf(max_px weight 255)) reaches 2^24 (the cells' sums have 24 bits; keep <= 8
+ * always fits).  At run: MVS_ESTATE when the depth store was re-sized since init or a listed slot is no longer filled.  All checks come
+ * before the first allocation; after an error nothing is written. */
+int mvs_propagate_set_consistency(mvs_ctx *ctx, int nslots, const int *slots, float weight, float max_px);
+void *mvs_propagate_support_device(mvs_ctx *ctx);
+int mvs_propagate_support_fetch(mvs_ctx *ctx, uint8_t *support_hw);
 int mvs_propagate_fetch(mvs_ctx *ctx, float *z_hw, float *gx_hw, float *gy_hw, unsigned int *cells_hw);
 void *mvs_propagate_depth_device(mvs_ctx *ctx);
 void *mvs_propagate_cost_device(mvs_ctx *ctx);

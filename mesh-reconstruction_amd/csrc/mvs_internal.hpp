@@ -22,6 +22,16 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// The table of the propagation's geometric term (propagate.hip) as the kernel reads it: per camera P then P^-1,
+// row-major -- the main camera first, then the neighbours --, each neighbour's depth map in the depth store, weight * 255 and the cap
+struct alignas(16) PropGeo {
+    float cam[9][32];
+    const float *map[8];
+    float w255, max_px;
+    int pad[2];
+};
+static_assert(sizeof(PropGeo) == 1232, "PropGeo is copied to the device and into LDS as 308 words");
+
 struct ProfileSlot {
     hipEvent_t start = nullptr, stop = nullptr;
     int kind = -1;
@@ -235,6 +245,14 @@ struct mvs_ctx {
     const void *prop_gate_guide = nullptr;
     int prop_tau = 255;
     bool prop_guide_own = false;
+    // its geometric term (section 27): what mvs_propagate_set_consistency recorded for the next init (prop_cons_n = 0: off), and what
+    // the last init took -- how many neighbours, their slots, the depth store's capacity then, and the host copy of the table the
+    // kernel reads, which sits behind the guide bytes and the H*W support bytes of prop_maps
+    int prop_cons_n = 0, prop_cons_slots[8] = {0};
+    float prop_cons_weight = 0.f, prop_cons_max_px = 0.f;
+    int prop_geo_n = 0, prop_geo_slots[8] = {0};
+    size_t prop_geo_cap = 0;
+    mvs::PropGeo prop_geo = {};
 
     // ---- profiling -----------------------------------------------------------------------------------
     bool profiling = false;

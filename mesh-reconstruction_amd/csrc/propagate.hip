@@ -20,7 +20,15 @@
 // The guide gate of DESIGN.md section 26 (mvs_propagate_set_gate) is two kernel arguments, not a template parameter: a member is live only
 // if its guide value is within tau of the centre's, read from a second byte tile in LDS (the main image again, or the stage's copy of the
 // caller's guide); tau = 255, the default, passes every member, so an ungated run computes what it computed without the gate.
+// The geometric term of DESIGN.md section 27 (mvs_propagate_set_consistency) is runtime arguments too: a candidate that has a counted view
+// is carried through the main camera's inverse into each listed neighbour of the depth store, takes the depth the neighbour's map holds
+// at the nearest pixel, comes back, and pays for the distance in pixels between where it left and where it returns (prop_consistency:
+// fusion's arithmetic, one gather per neighbour, the matrices read with wave-uniform addresses from the stage's table).  The number of
+// neighbours that answer travels with the hypothesis: a candidate that wins brings its count along, a pixel that keeps what it holds
+// keeps the byte the map has for it, so the support map is that of the held hypotheses after every launch at one evaluation per
+// candidate and none for the kept one.  With no neighbour listed the term is one wave-uniform branch per candidate.
 #include "bestk_rules.hpp"
+#include "depth_rules.hpp"
 
 #include <cmath>
 
@@ -44,7 +52,25 @@ struct PropArgs {
     uint32_t seed;                   // mix(seed + (2 t + h))
     int tau;                         // the gate of section 26: member q of p is live only if |G(q) - G(p)| <= tau (255: no gate)
     const uint8_t *guide;            // G, H*W; null: the main image
+    // the geometric term of section 27 (nslots = 0: none)
+    int nslots;
+    const PropGeo *geo;              // the term's table (mvs_internal.hpp); the support map, H*W u8, lies H*W bytes behind the cost map's end
 };
+
+// What the kernel needs rarely -- the random candidates' steps and seed, the counters' address at its end -- waits in LDS, not in scalar
+// registers held through the window loops: with eight list entries (KMAX = 8) the kernel has none to spare
+struct PropCold {
+    float dz, dg;
+    uint32_t seed, pad;
+    unsigned long long *counters;
+};
+
+constexpr int PROP_MAX_SLOTS = 8;
+constexpr int PROP_GEO_WORDS = sizeof(PropGeo) / 4;
+
+// where the table sits in the stage's allocation: behind the five maps, the guide bytes and the support bytes, on a 16-byte boundary
+inline size_t prop_table_at(size_t bytes_before) { return (bytes_before + 15) & ~(size_t)15; }
+inline size_t prop_tab_offset(size_t P) { return prop_table_at(22 * P); }
 
 __host__ __device__ __forceinline__ uint32_t prop_mix(uint32_t x)
 {
@@ -69,6 +95,63 @@ __device__ __forceinline__ bool prop_better(uint32_t c, uint32_t b)
     return (c >> 24) != 0u && (b == 0u || umul24u(c & 0xffffffu, b >> 24) < umul24u(b & 0xffffffu, c >> 24));
 }
 
+// the support byte of pixel `pix`: behind the cost map come the guide bytes, then the support bytes
+__device__ __forceinline__ uint8_t *prop_support_at(const SweepParams &p, const PropArgs &a, size_t pix)
+{
+    int W = p.W, H = p.H;
+    asm volatile("" : "+s"(W), "+s"(H));   // (computed where it is used, twice per pixel, not held in registers through the kernel)
+    const size_t P = (size_t)W * H;
+    return (uint8_t *)(a.cost + P) + P + pix;
+}
+
+// section 27, rules 2-6: the penalty g of the hypothesis depth cz at (row, col), in units of the cells' sums per counted view, and the
+// number of listed neighbours that answer for it.  f32, one rounding per operation, in fusion's order (depth_rules.hpp).  `geo` is the
+// table in LDS: every lane reads the same element, a broadcast.  No branches: a lane whose neighbour does not answer computes on a
+// valid address and discards what it gets (its wave would wait for the others anyway), which keeps the execution masks of three nested
+// tests out of the scalar registers.  The scheduling barriers keep the table's reads of one step from being issued ahead of the step
+// before it, so at most one camera matrix (16 registers) is live at a time
+__device__ __forceinline__ uint32_t prop_consistency(const SweepParams &p, const PropGeo *geo, int nslots, int row, int col, float cz, uint32_t &answers)
+{
+    // Nothing computed here may be taken for an invariant of the candidate loop and kept in registers through the window loops, where the
+    // kernel needs the most: the table's address, the pixel and the frame's size pass through empty asm statements, which the compiler
+    // cannot see through
+    int opaque = 0, W = p.W, H = p.H;
+    asm volatile("" : "+v"(opaque), "+v"(row), "+v"(col), "+s"(W), "+s"(H));
+    const PropGeo &g = *(const PropGeo *)((const char *)geo + opaque);
+    const float *M = g.cam[0];
+    const float halfW = (float)W * 0.5f, halfH = (float)H * 0.5f;
+    const float xn = __builtin_fmaf((float)(2 * col + 1), p.invW, -1.0f);
+    const float yn = __builtin_fmaf(-(float)(2 * row + 1), p.invH, 1.0f);
+    const float3 X = unproject(M + 16, xn, yn, cz);
+    const float max_px = g.max_px, w255 = g.w255;
+    uint32_t sum = 0u;
+    answers = 0u;
+#pragma unroll 1
+    for (int j = 0; j < nslots; j++) {
+        __builtin_amdgcn_sched_barrier(0);
+        const float *Pj = g.cam[j + 1];
+        const float qw = prow(Pj, 3, X);
+        const float ax = prow(Pj, 0, X) / qw, ay = prow(Pj, 1, X) / qw;
+        const float u = (ax + 1.0f) * halfW - 0.5f;
+        const float v = (1.0f - ay) * halfH - 0.5f;
+        const float fc = floorf(u + 0.5f), fr = floorf(v + 0.5f);
+        const bool in = qw > 0.f && fc >= 0.f && fc < (float)W && fr >= 0.f && fr < (float)H;       // false for NaN
+        const float zj = g.map[j][in ? (int)fr * W + (int)fc : 0];                                   // (the frame has fewer than 2^28 pixels)
+        __builtin_amdgcn_sched_barrier(0);
+        const float3 Xj = unproject(Pj + 16, ax, ay, zj);   // the continuous position with the nearest pixel's depth
+        __builtin_amdgcn_sched_barrier(0);
+        const float sw = prow(M, 3, Xj);
+        const float ur = (prow(M, 0, Xj) / sw + 1.0f) * halfW - 0.5f;
+        const float vr = (1.0f - prow(M, 1, Xj) / sw) * halfH - 0.5f;
+        const float du = ur - (float)col, dv = vr - (float)row;
+        const float d = sqrtf(du * du + dv * dv);
+        const bool answer = in && prop_inside(zj) && sw > 0.f && d <= max_px;   // rule 5 (d NaN: no)
+        answers += answer ? 1u : 0u;
+        sum += (uint32_t)floorf((answer ? d : max_px) * w255);
+    }
+    return sum / (uint32_t)nslots;
+}
+
 template <int COST, int R, int KMAX>
 __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, const uint32_t *__restrict__ lut_g, PropArgs a)
 {
@@ -79,6 +162,8 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
     __shared__ uint32_t lut[1024];
     __shared__ uint8_t mainl[S::SAMPLES];   // [HH][HW] the main image of tile + halo (0 outside the frame: such a member is never sampled)
     __shared__ uint8_t guidel[S::SAMPLES];  // [HH][HW] the gate's guide likewise: the main image again, or the stage's copy of the caller's
+    __shared__ PropGeo geol;                // section 27's table (filled only with a term)
+    __shared__ PropCold coldl;              // the arguments of the random candidates and the counters' address
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * ZN_TW, y0 = blockIdx.y * ZN_TH;
 #pragma unroll
@@ -92,6 +177,14 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
         mainl[i] = m;
         guidel[i] = (in && a.guide) ? a.guide[at] : m;
     }
+    if (tid == 0) {
+        coldl.dz = a.dz;
+        coldl.dg = a.dg;
+        coldl.seed = a.seed;
+        coldl.counters = a.counters;
+    }
+    if (a.nslots)
+        for (int i = tid; i < PROP_GEO_WORDS; i += ZN_THREADS) ((uint32_t *)&geol)[i] = ((const uint32_t *)a.geo)[i];
     __syncthreads();   // the only barrier: everything below is per thread
     const float hix = ZN_MAGIC + 132.0f + 256.0f * (float)p.W, hiy = ZN_MAGIC + 132.0f + 256.0f * (float)p.H;
     const bool init = a.half < 0;
@@ -132,11 +225,14 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
             } else {
                 ccls = PR_RANDOM;
                 if (prop_inside(z)) {
-                    const uint32_t base = prop_mix(a.seed ^ (uint32_t)(row * p.W + col));
+                    int opaque = 0;
+                    asm volatile("" : "+v"(opaque));   // (read here, per candidate, not once for the kernel and then held)
+                    const PropCold &cold = *(const PropCold *)((const char *)&coldl + opaque);
+                    const uint32_t base = prop_mix(cold.seed ^ (uint32_t)(row * p.W + col));
                     const uint32_t k = 4u * (uint32_t)(ci - 8);
-                    cz = z + a.dz * prop_uniform(prop_mix(base ^ k));
-                    cgx = gx + a.dg * prop_uniform(prop_mix(base ^ (k + 1u)));
-                    cgy = gy + a.dg * prop_uniform(prop_mix(base ^ (k + 2u)));
+                    cz = z + cold.dz * prop_uniform(prop_mix(base ^ k));
+                    cgx = gx + cold.dg * prop_uniform(prop_mix(base ^ (k + 1u)));
+                    cgy = gy + cold.dg * prop_uniform(prop_mix(base ^ (k + 2u)));
                 }
             }
             if (!prop_inside(cz)) continue;   // the centre is not live: cell 0
@@ -161,7 +257,7 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
 #pragma unroll 1
                     for (int dc = -R; dc <= R; dc++) {
                         const int qc = col + dc;
-                        const bool in = qc >= 0 && qc < p.W && qr >= 0 && qr < p.H;
+                        const bool in = (qc >= 0) & (qc < p.W) & (qr >= 0) & (qr < p.H);   // (no short circuit: one mask, no branch in the window loop)
                         const float zq = (cz + cgx * (float)dc) + zr;
                         const uint32_t gq = guidel[(ly + dr + R) * S::HW + lx + dc + R];
                         const bool gate = max(gq, g0) - min(gq, g0) <= (uint32_t)a.tau;
@@ -180,7 +276,16 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
                 }
                 acc.insert(C::cost(sum, centre_ok));
             }
-            const uint32_t cc = acc.cell(a.keep);
+            uint32_t cc = acc.cell(a.keep);
+            if (a.nslots && (init || (cc >> 24) != 0u)) {   // section 27, rule 7: k g on the sum (init: what it holds, counted or not, for the support map)
+                uint32_t answers;
+                const uint32_t g = prop_consistency(p, &geol, a.nslots, row, col, cz, answers), k = cc >> 24;
+                cc = k ? cc + k * g : 0u;
+                // rule 8: the count travels with the hypothesis.  A candidate that wins writes its own at once (the last winner's stays); a
+                // pixel that keeps what it holds keeps its byte; init, whose one candidate is what the pixel holds, writes it win or not
+                // (a pixel without a hypothesis never comes here: init's host side has cleared the map)
+                if (init || prop_better(cc, cell)) prop_support_at(p, a, pix)[0] = (uint8_t)answers;
+            }
             if (prop_better(cc, cell)) {
                 z = cz, gx = cgx, gy = cgy;
                 cell = cc;
@@ -198,7 +303,7 @@ __global__ __launch_bounds__(ZN_THREADS) void propagate_pass(SweepParams p, cons
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const unsigned long long m = __ballot(cls == k);
-            if (m != 0ull && (tid & 63) == 0) atomicAdd(a.counters + k, (unsigned long long)__popcll(m));
+            if (m != 0ull && (tid & 63) == 0) atomicAdd(coldl.counters + k, (unsigned long long)__popcll(m));
         }
     }
 }
@@ -272,6 +377,8 @@ void pass(mvs_ctx *ctx, PropArgs &a)
     a.keep = ctx->prop_keep;
     a.tau = ctx->prop_tau;
     a.guide = ctx->prop_guide_own ? (const uint8_t *)(maps + 5 * P) : nullptr;
+    a.nslots = ctx->prop_geo_n;
+    a.geo = (const PropGeo *)((const char *)maps + prop_tab_offset(P));
     SweepParams p;
     fill_params(ctx, p, ctx->prop_view_first, ctx->prop_view_count, ZN_TH, ZN_PC);
     if (ctx->prop_cost == MVS_COST_ZNCC)
@@ -285,6 +392,56 @@ int staged_state(mvs_ctx *ctx, const char *who)
 {
     if (!ctx->have_main || !ctx->have_views) return fail(ctx, MVS_ESTATE, "%s: set main view and side views first", who);
     if (ctx->sampler != MVS_SAMPLER_FIXED) return fail(ctx, MVS_ESTATE, "%s: implemented for MVS_SAMPLER_FIXED (the library default)", who);
+    return MVS_OK;
+}
+
+// section 27, rule 7: the largest penalty a candidate can get, floorf(max_px * weight * 255) (the setter admits up to 1 000 000)
+float consistency_cap(float weight, float max_px) { return floorf(max_px * (weight * 255.0f)); }
+
+// what init refuses with a term recorded; `tab` gets the table of rule 1 (the main camera's matrices made as a slot's are, the
+// neighbours' as their slots hold them, where their maps are), and nothing of the context changes
+int consistency_stage(mvs_ctx *ctx, const char *who, int keep, int view_count, PropGeo &tab)
+{
+    const int n = ctx->prop_cons_n, cap = (int)ctx->dstore.size();
+    if (cap == 0) return fail(ctx, MVS_ESTATE, "%s: a geometric term is recorded and there is no depth store (mvs_depth_store)", who);
+    for (int j = 0; j < n; j++) {
+        const int s = ctx->prop_cons_slots[j];
+        if (s >= cap) return fail(ctx, MVS_ESTATE, "%s: neighbour slot %d of the geometric term is outside the depth store (capacity %d)", who, s, cap);
+        if (!ctx->dstore[s].have) return fail(ctx, MVS_ESTATE, "%s: neighbour slot %d of the geometric term holds no depth map (mvs_depth_upload)", who, s);
+    }
+    mvs_ctx::DepthSlot m;
+    if (!slot_matrices(ctx->main_cam, m)) return fail(ctx, MVS_EINVAL, "%s: a geometric term is recorded and the main camera is singular or has no finite centre", who);
+    // the cells' 24-bit sums: k (65025 + g) must stay below 2^24 for every k the merge can give (rule 7 covers k <= 8)
+    const int kmax = keep == MVS_KEEP_ALL ? view_count : keep;
+    if ((double)kmax * (65025.0 + (double)consistency_cap(ctx->prop_cons_weight, ctx->prop_cons_max_px)) >= 16777216.0)
+        return fail(ctx, MVS_EINVAL, "%s: %d views under MVS_KEEP_ALL with a geometric term of up to %g per view overflow the cells' 24-bit sums (set keep <= 8)", who,
+                    view_count, (double)consistency_cap(ctx->prop_cons_weight, ctx->prop_cons_max_px));
+    const size_t P = (size_t)ctx->W * ctx->H;
+    memcpy(tab.cam[0], m.P, sizeof(m.P));
+    memcpy(tab.cam[0] + 16, m.Pi, sizeof(m.Pi));
+    for (int j = 0; j < n; j++) {
+        const mvs_ctx::DepthSlot &s = ctx->dstore[ctx->prop_cons_slots[j]];
+        memcpy(tab.cam[j + 1], s.P, sizeof(s.P));
+        memcpy(tab.cam[j + 1] + 16, s.Pi, sizeof(s.Pi));
+        tab.map[j] = (const float *)ctx->dstore_depth.ptr + P * ctx->prop_cons_slots[j];
+    }
+    tab.w255 = ctx->prop_cons_weight * 255.0f;
+    tab.max_px = ctx->prop_cons_max_px;
+    return MVS_OK;
+}
+
+// what run refuses with the term of the last init: the kernel reads the store's maps where they were then
+int consistency_current(mvs_ctx *ctx, const char *who)
+{
+    bool moved = ctx->dstore.size() != ctx->prop_geo_cap;
+    for (int j = 0; j < ctx->prop_geo_n && !moved; j++)   // (re-sized and back: the buffers grow only, but they may have moved)
+        moved = ctx->prop_geo.map[j] != (const float *)ctx->dstore_depth.ptr + (size_t)ctx->W * ctx->H * ctx->prop_geo_slots[j];
+    if (moved)
+        return fail(ctx, MVS_ESTATE, "%s: the depth store was re-sized since mvs_propagate_init took its geometric term (capacity %d then, %d now)", who,
+                    (int)ctx->prop_geo_cap, (int)ctx->dstore.size());
+    for (int j = 0; j < ctx->prop_geo_n; j++)
+        if (!ctx->dstore[ctx->prop_geo_slots[j]].have)
+            return fail(ctx, MVS_ESTATE, "%s: neighbour slot %d of the geometric term holds no depth map any more", who, ctx->prop_geo_slots[j]);
     return MVS_OK;
 }
 
@@ -311,9 +468,13 @@ int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int 
         return fail(ctx, MVS_EINVAL, "%s: view range [%d,%d) outside 0..%d", who, view_first, view_first + view_count, ctx->V);
     if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler's cells hold at most 255 views (have %d)", who, ctx->V);
     if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler addresses images of up to 16383 x 16383", who);
+    PropGeo tab = {};
+    if (ctx->prop_cons_n > 0 && (rc = consistency_stage(ctx, who, keep, view_count, tab))) return rc;
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)ctx->W * ctx->H;
-    if ((rc = ensure(ctx, ctx->prop_maps, 5 * P * sizeof(float) + P))) return rc;   // z, gx, gy, the cells, the cost map; the gate's guide (u8)
+    const size_t maps_bytes = 5 * P * sizeof(float) + P;   // z, gx, gy, the cells, the cost map; the gate's guide (u8)
+    // behind them the support map (u8) and, on a 16-byte boundary, the geometric term's table
+    if ((rc = ensure(ctx, ctx->prop_maps, prop_table_at(maps_bytes + P) + sizeof(PropGeo)))) return rc;
     if ((rc = ensure(ctx, ctx->prop_counters, 4 * sizeof(unsigned long long)))) return rc;
     if ((rc = ensure_fx_lut(ctx))) return rc;
     ctx->prop_cost = cost;
@@ -326,6 +487,14 @@ int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int 
     ctx->prop_guide_own = ctx->prop_gate_guide != nullptr;
     float *maps = (float *)ctx->prop_maps.ptr;
     if (ctx->prop_guide_own) MVS_HIP(ctx, hipMemcpyAsync(maps + 5 * P, ctx->prop_gate_guide, P, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->prop_geo_n = ctx->prop_cons_n;
+    ctx->prop_geo_cap = ctx->dstore.size();
+    if (ctx->prop_geo_n > 0) {
+        memcpy(ctx->prop_geo_slots, ctx->prop_cons_slots, sizeof(ctx->prop_geo_slots));
+        ctx->prop_geo = tab;   // the copy below reads the context's table, which lives as long as the stage
+        MVS_HIP(ctx, hipMemcpyAsync((char *)maps + prop_tab_offset(P), &ctx->prop_geo, sizeof(PropGeo), hipMemcpyHostToDevice, ctx->stream));
+    }
+    MVS_HIP(ctx, hipMemsetAsync((uint8_t *)(maps + 5 * P) + P, 0, P, ctx->stream));   // rule 8: 0 without a term, and for a pixel without a hypothesis
     MVS_HIP(ctx, hipMemsetAsync(ctx->prop_counters.ptr, 0, 4 * sizeof(unsigned long long), ctx->stream));
     {
         ProfileScope ps(ctx, MVS_K_SWEEP);
@@ -354,6 +523,7 @@ int mvs_propagate_run(mvs_ctx *ctx, int iterations, float dz, float dg, int nran
     if (ctx->prop_view_first + ctx->prop_view_count > ctx->V)
         return fail(ctx, MVS_ESTATE, "%s: the views changed since mvs_propagate_init: its range [%d,%d) is outside 0..%d", who, ctx->prop_view_first,
                     ctx->prop_view_first + ctx->prop_view_count, ctx->V);
+    if (ctx->prop_geo_n > 0 && (rc = consistency_current(ctx, who))) return rc;
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_fx_lut(ctx))) return rc;
     {
@@ -386,6 +556,40 @@ int mvs_propagate_set_gate(mvs_ctx *ctx, int tau, const void *guide_dev)
     if (tau < 0 || tau > 255) return fail(ctx, MVS_EINVAL, "mvs_propagate_set_gate: tau %d outside 0..255", tau);
     ctx->prop_gate_tau = tau;
     ctx->prop_gate_guide = guide_dev;
+    return MVS_OK;
+}
+
+int mvs_propagate_set_consistency(mvs_ctx *ctx, int nslots, const int *slots, float weight, float max_px)
+{
+    static const char who[] = "mvs_propagate_set_consistency";
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
+    if (nslots < 0 || nslots > PROP_MAX_SLOTS) return fail(ctx, MVS_EINVAL, "%s: nslots %d outside 0..%d", who, nslots, PROP_MAX_SLOTS);
+    if (nslots > 0) {
+        if (!slots) return fail(ctx, MVS_EINVAL, "%s: slots is null", who);
+        for (int j = 0; j < nslots; j++)
+            if (slots[j] < 0) return fail(ctx, MVS_EINVAL, "%s: slot %d is negative", who, slots[j]);
+        if (!(weight >= 0.0f) || !std::isfinite(weight)) return fail(ctx, MVS_EINVAL, "%s: weight %g negative or not finite", who, (double)weight);
+        if (!(max_px > 0.0f) || !std::isfinite(max_px)) return fail(ctx, MVS_EINVAL, "%s: max_px %g not positive or not finite", who, (double)max_px);
+        if (!(consistency_cap(weight, max_px) <= 1000000.0f))
+            return fail(ctx, MVS_EINVAL, "%s: floor(max_px * weight * 255) = %g above 1000000: the cells' sums have 24 bits", who, (double)consistency_cap(weight, max_px));
+    }
+    ctx->prop_cons_n = nslots;
+    for (int j = 0; j < PROP_MAX_SLOTS; j++) ctx->prop_cons_slots[j] = j < nslots ? slots[j] : 0;
+    ctx->prop_cons_weight = nslots > 0 ? weight : 0.0f;
+    ctx->prop_cons_max_px = nslots > 0 ? max_px : 0.0f;
+    return MVS_OK;
+}
+
+void *mvs_propagate_support_device(mvs_ctx *ctx) { return ctx && ctx->prop_have ? (uint8_t *)((float *)ctx->prop_maps.ptr + 5 * (size_t)ctx->W * ctx->H) + (size_t)ctx->W * ctx->H : nullptr; }
+
+int mvs_propagate_support_fetch(mvs_ctx *ctx, uint8_t *support_hw)
+{
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_propagate_support_fetch: null context");
+    if (!support_hw) return fail(ctx, MVS_EINVAL, "mvs_propagate_support_fetch: support_hw is null");
+    if (!ctx->prop_have) return fail(ctx, MVS_ESTATE, "mvs_propagate_support_fetch: no hypotheses yet (mvs_propagate_init first)");
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    MVS_HIP(ctx, hipMemcpyAsync(support_hw, mvs_propagate_support_device(ctx), (size_t)ctx->W * ctx->H, hipMemcpyDeviceToHost, ctx->stream));
+    MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MVS_OK;
 }
 

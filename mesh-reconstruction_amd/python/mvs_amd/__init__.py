@@ -154,6 +154,9 @@ ABI = [
     ("mvs_propagate_init", _i, [_vp, _vp, _i, _i, _i, _i, _i, _f, C.c_uint]),
     ("mvs_propagate_run", _i, [_vp, _i, _f, _f, _i, C.c_uint]),
     ("mvs_propagate_set_gate", _i, [_vp, _i, _vp]),
+    ("mvs_propagate_set_consistency", _i, [_vp, _i, _i32p, _f, _f]),
+    ("mvs_propagate_support_device", _vp, [_vp]),
+    ("mvs_propagate_support_fetch", _i, [_vp, _u8p]),
     ("mvs_propagate_fetch", _i, [_vp, _fp, _fp, _fp, C.POINTER(C.c_uint32)]),
     ("mvs_propagate_depth_device", _vp, [_vp]),
     ("mvs_propagate_cost_device", _vp, [_vp]),
@@ -468,17 +471,30 @@ def _propagate_step(ctx, depth_ptr, propagate, cost, step, fetch):
     """the `propagate` keyword of the coarse-to-fine helpers: propagate_init + propagate_run on the map at depth_ptr with the windowed cost
     `cost` = (MVS_COST_*, radius, keep); the random steps are dz_steps / dg_steps plane steps `step` of the level that selected the map
     -> the z map (fetch) or None (it stays at propagate_depth_pointer())"""
-    unknown = set(propagate) - {"iterations", "dz_steps", "dg_steps", "nrandom", "seed", "slopes", "tau"}
+    unknown = set(propagate) - {"iterations", "dz_steps", "dg_steps", "nrandom", "seed", "slopes", "tau", "consistency"}
     if unknown:
-        raise ValueError("propagate: unknown keys %s (iterations, dz_steps, dg_steps, nrandom, seed, slopes, tau)" % sorted(unknown))
+        raise ValueError("propagate: unknown keys %s (iterations, dz_steps, dg_steps, nrandom, seed, slopes, tau, consistency)" % sorted(unknown))
     if cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
-    if "tau" in propagate:      # the guide gate (DESIGN.md section 26), the guide the staged main image; init takes it, so 255 goes back at once
-        ctx.propagate_set_gate(int(propagate["tau"]))
+    consistency = propagate.get("consistency")
+    if consistency is not None:
+        unknown = set(consistency) - {"slots", "weight", "max_px"}
+        if unknown:
+            raise ValueError("propagate: consistency: unknown keys %s (slots, weight, max_px)" % sorted(unknown))
+    if "tau" in propagate or consistency is not None:
+        # the guide gate (DESIGN.md section 26; the guide the staged main image) and the geometric term (section 27): init takes what is
+        # recorded, so the defaults go back at once
         try:
+            if "tau" in propagate:
+                ctx.propagate_set_gate(int(propagate["tau"]))
+            if consistency is not None:
+                ctx.propagate_set_consistency(**consistency)
             ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
         finally:
-            ctx.propagate_set_gate(255)
+            if "tau" in propagate:
+                ctx.propagate_set_gate(255)
+            if consistency is not None:
+                ctx.propagate_set_consistency(())
     else:
         ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
     ctx.propagate_run(int(propagate.get("iterations", 3)), float(np.float32(float(propagate.get("dz_steps", 0.5)) * step)),
@@ -510,7 +526,9 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     of the edge pixels does not fall, and random steps of a coarse plane step raise it).  The optional key tau=0..255 gates the
     propagation's windows on the staged main image (Context.propagate_set_gate before the init, 255 restored after it; DESIGN.md section
     26): the gated propagation does repair the edge pixels of a map an ungated sweep made, wherever the step is an intensity edge.
-    cost=dict(..., tau=) raises ValueError: the band level has no gate."""
+    cost=dict(..., tau=) raises ValueError: the band level has no gate.  The optional key consistency=dict(slots=, weight=, max_px=)
+    adds the geometric term against neighbour maps in the depth store (Context.propagate_set_consistency before the init, off again
+    after it; DESIGN.md section 27, with its warning: consistently wrong neighbours confirm each other)."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     if propagate is not None and cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
@@ -563,7 +581,8 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
     needs cost=: the finest level's final map becomes the start of ctxs[0].propagate_init / propagate_run and the propagated z map is
     returned in its place (fetch=False: it stays at ctxs[0].propagate_depth_pointer()).  WARNING, as there: propagation does not help
     beside depth steps, where a window prefers the nearer surface; it spreads that preference -- unless it is gated with the optional
-    key tau=, as there."""
+    key tau=, as there.  The optional key consistency=dict(slots=, weight=, max_px=) adds section 27's geometric term on ctxs[0], as
+    there."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     if propagate is not None and cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
@@ -602,6 +621,53 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
         if depth_ptr is None:
             depth_ptr = ctxs[0].sweep_result_pointers()[0]      # one level: the refined global sweep's map
         out = _propagate_step(ctxs[0], depth_ptr, propagate, cost, step, fetch)
+    return out
+
+
+def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coarse_planes, z_lo=-1.0, z_hi=1.0, cost=None, propagate=None,
+                        consistency=None, fetch=True):
+    """Geometric propagation over frames of the frame store: main_slots [n] frame-store slots with their cameras
+    main_cams [n,4,4]; side_slots [n,S] and side_cams [n,S,4,4] the side views of each.  The depth store must have 2 n slots
+    (Context.depth_store); nothing else is allocated beyond what the calls below allocate.
+    Stage 1, for every main frame i: Context.sweep_handles stages its views, sweep_run_bestk with cost=dict(cost=, radius=, keep=) over
+    `coarse_planes` planes of [z_lo, z_hi], refined, then the photometric propagation of propagate=dict(iterations=, dz_steps=,
+    dg_steps=, nrandom=, seed=, slopes=, tau=) as in coarse_to_fine (the steps in coarse plane steps); its z and cost maps go device to
+    device into depth slot i.
+    Stage 2, for every main frame i: the term consistency=dict(weight=, max_px=) on the stage-1 slots of those of its side views that
+    are main frames themselves, propagate_init from its own slot i, propagate_run; the z and cost maps go into slot n + i.
+    The term (and the gate) are off again on return -> the n stage-2 z maps [n,H,W] float32 (fetch=False: None, they are in the slots).
+    WARNING: the neighbours' maps are estimated the same way as the map they correct: consistently wrong neighbours confirm each other,
+    and the gain at depth steps is small (section 27 has the figures)."""
+    if cost is None:
+        raise ValueError("propagate_two_stage: needs cost=dict(cost=, radius=, keep=), the windowed cost of the sweep and the propagation")
+    propagate = dict(propagate or {})
+    if "consistency" in propagate:
+        raise ValueError("propagate_two_stage: the term goes into consistency=dict(weight=, max_px=); its slots are the stage-1 slots")
+    consistency = dict(consistency or {})
+    unknown = set(consistency) - {"weight", "max_px"}
+    if unknown:
+        raise ValueError("consistency: unknown keys %s (weight, max_px)" % sorted(unknown))
+    ms = [int(s) for s in np.asarray(main_slots).reshape(-1)]
+    n = len(ms)
+    ss = np.asarray(side_slots, dtype=np.int32).reshape(n, -1)
+    mc = np.asarray(main_cams, dtype=np.float32).reshape(n, 4, 4)
+    sc = np.asarray(side_cams, dtype=np.float32).reshape(n, ss.shape[1], 4, 4)
+    cost = _cost_args(cost)
+    step = (float(z_hi) - float(z_lo)) / coarse_planes
+    out = np.empty((n, ctx.H, ctx.W), np.float32) if fetch else None
+    for stage in (0, 1):
+        for i in range(n):
+            ctx.sweep_handles(ms[i], mc[i], ss[i], sc[i], coarse_planes, z_lo, z_hi)
+            if stage == 0:
+                ctx.sweep_run_bestk(*cost, 0, None, MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN)
+                ctx.sweep_refine_depth()
+                _propagate_step(ctx, ctx.sweep_result_pointers()[0], propagate, cost, step, False)
+            else:
+                slots = [ms.index(int(s)) for s in ss[i] if int(s) in ms]
+                _propagate_step(ctx, ctx.depth_slot_pointer(i), dict(propagate, consistency=dict(consistency, slots=slots)), cost, step, False)
+                if fetch:
+                    out[i] = ctx.propagate_fetch()[0]
+            ctx.depth_upload_device(stage * n + i, mc[i], ctx.propagate_depth_pointer(), ctx.propagate_cost_pointer())
     return out
 
 
@@ -1382,6 +1448,29 @@ class Context:
         address of H*W uint8, copied by that init; None = the staged main image).  The same warning about a small tau as
         sweep_run_bestk_gated"""
         self._check(self.lib.mvs_propagate_set_gate(self.h, int(tau), C.c_void_p(int(guide_ptr)) if guide_ptr else None))
+
+    def propagate_set_consistency(self, slots, weight=0.0, max_px=1.0):
+        """mvs_propagate_set_consistency: records the geometric term the NEXT propagate_init takes (and the propagate_run calls behind
+        it use).  slots: up to 8 slots of the depth store holding the neighbouring views' depth maps and cameras (read when the kernels
+        run, not copied); a hypothesis pays `weight` grey levels of the cost map's scale (ZNCC: 127.5 (1 - ncc)) per pixel of forward /
+        backward reprojection error against each neighbour, capped at max_px pixels and averaged over the neighbours, and
+        propagate_support() counts per pixel the neighbours within max_px.  slots=() turns the term off (the default).  WARNING:
+        consistently wrong neighbours confirm each other"""
+        s = np.ascontiguousarray(np.asarray(list(slots), dtype=np.int32).reshape(-1))
+        self._check(self.lib.mvs_propagate_set_consistency(self.h, len(s), _ptr(s, _i32p) if len(s) else None, float(weight), float(max_px)))
+
+    def propagate_support(self, fetch=True):
+        """mvs_propagate_support_fetch -> (H, W) uint8: the listed neighbours that confirm the hypothesis each pixel holds (all 0 without
+        a geometric term); synchronises.  fetch=False: the map's device address (propagate_support_pointer())"""
+        if not fetch:
+            return self.propagate_support_pointer()
+        out = np.empty((self.H, self.W), np.uint8)
+        self._check(self.lib.mvs_propagate_support_fetch(self.h, _ptr(out, _u8p)))
+        return out
+
+    def propagate_support_pointer(self):
+        """device address of the support map, H*W uint8 (0 before the first propagate_init)"""
+        return self.lib.mvs_propagate_support_device(self.h) or 0
 
     def propagate_run(self, iterations, dz, dg, nrandom=2, seed=0):
         """mvs_propagate_run: `iterations` PatchMatch iterations on the hypotheses of propagate_init.  In each of an iteration's two
