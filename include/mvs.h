@@ -881,6 +881,58 @@ int mvs_tsdf_shade_fetch(mvs_ctx *ctx, uint8_t *shaded_hw2);
 int mvs_tsdf_sample_appearance(mvs_ctx *ctx, const float *points4 /* n x 4 */, int n, float *out /* n */);
 void *mvs_depth_slot_device(mvs_ctx *ctx, int slot);
 
+/* ---- support planes, masked fusion and sequence fusion (csrc/fuse.hip, csrc/fuse_sequence.hip, csrc/tsdf.hip) ----
+ * A support plane is H * W bytes of u8 per depth slot: how many neighbour maps confirm the depth each pixel of the stored map holds, e.g.
+ * the propagation's support map (mvs_propagate_support_device).  All planes live in one buffer of `capacity` planes, allocated by the first
+ * support upload after mvs_depth_store and freed by mvs_depth_store (re-sizing empties the store).  Uploads are stream-ordered like
+ * mvs_depth_upload*; mvs_depth_support_fetch synchronises.  mvs_depth_upload / mvs_depth_upload_device into a slot drop that slot's plane
+ * (a flag, not a copy: a new map is not described by the old bytes).  MVS_EINVAL: NULL argument, slot outside the store; MVS_ESTATE: upload
+ * into a slot without a depth map, fetch from a slot without a plane; MVS_ENOMEM.  A refused call leaves the context usable.
+ *
+ * Rule 1s replaces fusion rule 1 wherever a min_support (0..255) is given: a stored pixel p is valid when rule 1 holds and, for
+ * min_support > 0, support[p] >= min_support.  With min_support > 0 every slot involved must have a plane (else MVS_ESTATE); with
+ * min_support = 0 planes are not read and need not exist.  Rule 1s is the same as overwriting the stored depth with the empty value 1.0
+ * wherever the support is too low.
+ *
+ * mvs_fuse_depth_masked is mvs_fuse_depth with rule 1s in the three places it reads a stored depth: the reference pixel, its four tangent
+ * neighbours, and the neighbour map's pixel of rule 3.  It fills the same buffers (mvs_fuse_points_device returns its rows).
+ * mvs_tsdf_integrate_masked is mvs_tsdf_integrate (frame_slots NULL) or mvs_tsdf_integrate_frames with rule 1s in the w-map pass: a masked
+ * pixel's w is NaN.  With min_support = 0 both write the bytes of the calls they extend.
+ *
+ * mvs_fuse_sequence fuses a list of references into one cloud in which every surface point appears once:
+ *   S1 Every distinct slot named in the call has a claim plane of H * W bytes, all zero when the call starts.
+ *   S2 References are taken in list order.  For reference i, rules 1s-5 of mvs_fuse_depth_masked run with its row of neighbours
+ *      (neighbour_slots[i * nneighbours ...]); a -1 entry is skipped, a neighbour listed twice votes twice.  A pixel p is KEPT when those
+ *      rules keep it and claim_ref[p] == 0.  Claims gate nothing else: a claimed pixel is still a tangent neighbour and still votes in
+ *      other references' rule 3 -- it is surface, only not a new point.
+ *   S3 For every kept pixel and every neighbour j that agreed in rule 3: claim_j[(r_j, c_j)] = 1, at the pixel rule 3 read.  Dropped
+ *      pixels claim nothing.
+ *   S4 Rows are (x, y, z, 1, nx, ny, nz); reference i's rows come in ascending pixel index, behind reference i - 1's.  A row whose index
+ *      is >= max_rows is not written; *out_count is the total either way and out_ref_counts[i] reference i's count.  Claims are made
+ *      whether or not the row fitted: calling again with a larger max_rows gives the same rows, because S1 clears the planes.
+ *      max_rows = 0 with a NULL out_points7 is a counting call.
+ *   S5 The result is determinate: the launches of reference i read only claim plane ref_i and write only planes of slots other than
+ *      ref_i (a neighbour equal to its reference is refused, as in mvs_fuse_depth), every write stores the value 1, and the launches are
+ *      stream-ordered.
+ * The host does not wait between references: the running total lives in device memory and the call synchronises once (totals and
+ * per-reference counts) plus once for the optional row download; row offsets are 64-bit.  out_points7 NULL with max_rows > 0 leaves the
+ * rows on the device (mvs_fuse_sequence_points_device).  Errors beside mvs_fuse_depth's: nrefs outside 1..capacity, a reference listed
+ * twice, nneighbours outside 0..16, min_support outside 0..255, negative max_rows; MVS_ENOMEM.
+ * Out of scope: weights in the TSDF sum, a per-row view count, the propagation's geometric term reading the neighbours' planes, batching
+ * references that share no slot into one launch. */
+int mvs_depth_support_upload(mvs_ctx *ctx, int slot, const uint8_t *support_hw);
+int mvs_depth_support_upload_device(mvs_ctx *ctx, int slot, const void *support_dev); /* e.g. mvs_propagate_support_device(ctx) */
+int mvs_depth_support_fetch(mvs_ctx *ctx, int slot, uint8_t *support_hw);
+int mvs_depth_support_drop(mvs_ctx *ctx, int slot);
+int mvs_fuse_depth_masked(mvs_ctx *ctx, int ref_slot, int nneighbours, const int *neighbour_slots, int min_consistent, float max_reproj_px,
+                          float max_rel_depth, float max_cost, int min_support, float *out_points7, int *out_count);
+int mvs_tsdf_integrate_masked(mvs_ctx *ctx, int n, const int *depth_slots, const int *frame_slots /* nullable: no appearance */, float max_cost,
+                              int min_support);
+int mvs_fuse_sequence(mvs_ctx *ctx, int nrefs, const int *ref_slots, int nneighbours, const int *neighbour_slots /* nrefs x nneighbours, -1 = none */,
+                      int min_consistent, float max_reproj_px, float max_rel_depth, float max_cost, int min_support, long long max_rows,
+                      float *out_points7 /* nullable: max_rows x 7 */, int *out_ref_counts /* nullable: nrefs */, long long *out_count);
+void *mvs_fuse_sequence_points_device(mvs_ctx *ctx); /* the rows of the last call, min(total, max_rows) of them; NULL before the first */
+
 /* ---- one main view on several GPUs of one node (SURVEY.md section 8b "multi-GPU", 8e, north_star) -----------------------------
  * A communicator owns one context per listed device and one RCCL communicator across them (librccl is loaded when the first
  * communicator is created; the library has no link dependency on it).  mvs_sweep_sharded runs ONE main view on all of them, one host

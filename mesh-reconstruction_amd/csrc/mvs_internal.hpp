@@ -177,12 +177,18 @@ struct mvs_ctx {
     // and the camera's matrices as the fusion kernels use them (host copy; they travel as kernel arguments)
     struct DepthSlot {
         bool have = false, have_cost = false;
+        bool have_support = false;  // the slot's plane of dstore_support describes the stored map (mvs_depth_support_upload; a depth upload clears it)
         float P[16], Pi[16], C[4];
     };
     mvs::DevBuf dstore_depth, dstore_cost;
+    mvs::DevBuf dstore_support;  // support planes (section 28): capacity planes of H*W u8, made by the first support upload, freed by mvs_depth_store
     std::vector<DepthSlot> dstore;
     mvs::DevBuf fuse_rows, fuse_counts, fuse_scan;  // rows of the last mvs_fuse_depth; per-segment keep counts and their offsets; scan scratch
     bool fuse_have_rows = false;
+    // sequence fusion (fuse_sequence.hip: mvs_fuse_sequence, section 28): the rows of the last call; one H*W u8 claim plane per distinct slot
+    // it named; the running total (i64) followed by the per-reference counts (i32).  All three are made by the first call that needs them.
+    mvs::DevBuf fuse_seq_rows, fuse_seq_claims, fuse_seq_state;
+    bool fuse_seq_have_rows = false;
     // TSDF volume (tsdf.hip: mvs_tsdf_volume / mvs_tsdf_integrate / mvs_tsdf_surface): G^3 f32 sums then G^3 i32 counts; the w-maps of one
     // integration launch; the field and support mask mvs_tsdf_surface meshes.  tsdf_G = 0: no volume yet.
     mvs::DevBuf tsdf_vol, tsdf_wmaps, tsdf_work;

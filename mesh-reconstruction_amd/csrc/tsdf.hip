@@ -20,6 +20,10 @@
 //                                 cell (count << 24 | sum of u8 intensities) is read once, voted into where -1 <= t < 1, written once.
 // Both pairs share their bodies (wmap_value, integrate_node<bool>), so the TSDF fields come out the same bytes either way.
 //
+// mvs_tsdf_integrate_masked is either pair with rule 1s in the w-map pass (tsdf_wmap_masked_kernel,
+// tsdf_wmap_frames_masked_kernel: w = NaN where the slot's support plane is below min_support); with min_support = 0 it launches the
+// unmasked kernels.
+//
 // Arithmetic: f32, one rounding per operation, no contraction (the library builds with -ffp-contract=off; the pixel centres' fmaf is the
 // sweep's and is written out); tests/tsdf_mirror.py restates it in numpy, bit for bit.
 #include "depth_rules.hpp"
@@ -90,6 +94,31 @@ __global__ __launch_bounds__(256) void tsdf_wmap_frames_kernel(const WmapArgs a,
     if (p >= a.W * a.H) return;
     const int r = p / a.W, c = p - r * a.W;
     const float w = wmap_value(a, s, p, r, c);
+    reinterpret_cast<float2 *>(a.wmap)[(size_t)s * a.W * a.H + p] = make_float2(w, __uint_as_float((uint32_t)f.raw[s][p]));
+}
+
+// rule 1s in the w-map pass: the two kernels above with the chunk's support planes beside the maps -- a pixel whose
+// support is below min_support (> 0 here) has w = NaN, exactly as if its stored depth were the empty value 1.0, so the integration kernels
+// do not change.  mvs_tsdf_integrate_masked launches these only for min_support > 0.
+struct WmapMask {
+    const uint8_t *support[kTsdfChunk];
+    int min_support;
+};
+
+__global__ __launch_bounds__(256) void tsdf_wmap_masked_kernel(const WmapArgs a, const WmapMask m)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (p >= a.W * a.H) return;
+    const int r = p / a.W, c = p - r * a.W;
+    a.wmap[(size_t)s * a.W * a.H + p] = (int)m.support[s][p] < m.min_support ? __builtin_nanf("") : wmap_value(a, s, p, r, c);
+}
+
+__global__ __launch_bounds__(256) void tsdf_wmap_frames_masked_kernel(const WmapArgs a, const FrameArgs f, const WmapMask m)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (p >= a.W * a.H) return;
+    const int r = p / a.W, c = p - r * a.W;
+    const float w = (int)m.support[s][p] < m.min_support ? __builtin_nanf("") : wmap_value(a, s, p, r, c);
     reinterpret_cast<float2 *>(a.wmap)[(size_t)s * a.W * a.H + p] = make_float2(w, __uint_as_float((uint32_t)f.raw[s][p]));
 }
 
@@ -226,13 +255,14 @@ int tsdf_ensure_appearance(mvs_ctx *ctx)
 
 namespace {
 
-// mvs_tsdf_integrate (frames = false: frame_slots is not looked at) and mvs_tsdf_integrate_frames
-int tsdf_integrate_impl(mvs_ctx *ctx, const char *who, int nslots, const int *slots, const int *frame_slots, bool frames, float max_cost)
+// mvs_tsdf_integrate (frames = false: frame_slots is not looked at), mvs_tsdf_integrate_frames and, with a min_support, mvs_tsdf_integrate_masked
+int tsdf_integrate_impl(mvs_ctx *ctx, const char *who, int nslots, const int *slots, const int *frame_slots, bool frames, float max_cost, int min_support = 0)
 {
     if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
     if (!slots || (frames && !frame_slots)) return fail(ctx, MVS_EINVAL, "%s: slots is null", who);
     if (nslots < 1) return fail(ctx, MVS_EINVAL, "%s: nslots %d < 1", who, nslots);
     if (!(max_cost >= 0.f)) return fail(ctx, MVS_EINVAL, "%s: max_cost %g must be >= 0", who, max_cost);
+    if (min_support < 0 || min_support > 255) return fail(ctx, MVS_EINVAL, "%s: min_support %d out of range 0..255", who, min_support);
     if (!ctx->tsdf_G) return fail(ctx, MVS_ESTATE, "%s: no volume (mvs_tsdf_volume first)", who);
     const int cap = (int)ctx->dstore.size();
     for (int e = 0; e < nslots; e++)
@@ -246,6 +276,8 @@ int tsdf_integrate_impl(mvs_ctx *ctx, const char *who, int nslots, const int *sl
         if (!s.have) return fail(ctx, MVS_ESTATE, "%s: slot %d holds no depth map (mvs_depth_upload)", who, slots[e]);
         if (use_cost && !s.have_cost) return fail(ctx, MVS_ESTATE, "%s: max_cost %g is finite but slot %d was stored without a cost map", who, max_cost, slots[e]);
         if (frames && !ctx->store_have[(size_t)frame_slots[e]]) return fail(ctx, MVS_ESTATE, "%s: frame slot %d holds no frame (mvs_frame_upload)", who, frame_slots[e]);
+        if (min_support > 0 && !s.have_support)
+            return fail(ctx, MVS_ESTATE, "%s: min_support %d > 0 but slot %d has no support plane (mvs_depth_support_upload)", who, min_support, slots[e]);
     }
     MVS_HIP(ctx, hipSetDevice(ctx->device));
     const int W = ctx->W, H = ctx->H, G = ctx->tsdf_G;
@@ -259,6 +291,9 @@ int tsdf_integrate_impl(mvs_ctx *ctx, const char *who, int nslots, const int *sl
     WmapArgs wa;
     FrameArgs fa;
     IntegrateArgs ia;
+    WmapMask wm;
+    memset(&wm, 0, sizeof(wm));
+    wm.min_support = min_support;
     memset(&wa, 0, sizeof(wa));
     memset(&fa, 0, sizeof(fa));
     memset(&ia, 0, sizeof(ia));
@@ -295,15 +330,18 @@ int tsdf_integrate_impl(mvs_ctx *ctx, const char *who, int nslots, const int *sl
             memcpy(ia.P[e], s.P, 8 * sizeof(float));           // rows x, y
             memcpy(ia.P[e] + 8, s.P + 12, 4 * sizeof(float));  // row w
             if (frames) fa.raw[e] = (const uint8_t *)ctx->store_raw.ptr + P * frame_slots[e0 + e];
+            if (min_support > 0) wm.support[e] = (const uint8_t *)ctx->dstore_support.ptr + P * slot;
         }
         ia.n = n;
         const dim3 wgrid((unsigned)div_up((int)P, 256), (unsigned)n);
         if (frames) {
-            tsdf_wmap_frames_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa, fa);
+            if (min_support > 0) tsdf_wmap_frames_masked_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa, fa, wm);
+            else tsdf_wmap_frames_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa, fa);
             MVS_HIP(ctx, hipGetLastError());
             tsdf_integrate_frames_kernel<<<igrid, kTsdfTX * kTsdfTY, 0, ctx->stream>>>(ia, sum, count, (uint32_t *)ctx->tsdf_app.ptr);
         } else {
-            tsdf_wmap_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa);
+            if (min_support > 0) tsdf_wmap_masked_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa, wm);
+            else tsdf_wmap_kernel<<<wgrid, 256, 0, ctx->stream>>>(wa);
             MVS_HIP(ctx, hipGetLastError());
             tsdf_integrate_kernel<<<igrid, kTsdfTX * kTsdfTY, 0, ctx->stream>>>(ia, sum, count);
         }
@@ -353,6 +391,11 @@ int mvs_tsdf_integrate(mvs_ctx *ctx, int nslots, const int *slots, float max_cos
 int mvs_tsdf_integrate_frames(mvs_ctx *ctx, int n, const int *depth_slots, const int *frame_slots, float max_cost)
 {
     return tsdf_integrate_impl(ctx, "mvs_tsdf_integrate_frames", n, depth_slots, frame_slots, true, max_cost);
+}
+
+int mvs_tsdf_integrate_masked(mvs_ctx *ctx, int n, const int *depth_slots, const int *frame_slots, float max_cost, int min_support)
+{
+    return tsdf_integrate_impl(ctx, "mvs_tsdf_integrate_masked", n, depth_slots, frame_slots, frame_slots != nullptr, max_cost, min_support);
 }
 
 int mvs_tsdf_fetch(mvs_ctx *ctx, float *sdf_sum, int32_t *count)

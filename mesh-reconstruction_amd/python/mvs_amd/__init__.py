@@ -103,6 +103,14 @@ ABI = [
     ("mvs_depth_upload_device", _i, [_vp, _i, _fp, _vp, _vp]),
     ("mvs_fuse_depth", _i, [_vp, _i, _i, _i32p, _i, _f, _f, _f, _fp, C.POINTER(_i)]),
     ("mvs_fuse_points_device", _vp, [_vp]),
+    ("mvs_depth_support_upload", _i, [_vp, _i, _u8p]),
+    ("mvs_depth_support_upload_device", _i, [_vp, _i, _vp]),
+    ("mvs_depth_support_fetch", _i, [_vp, _i, _u8p]),
+    ("mvs_depth_support_drop", _i, [_vp, _i]),
+    ("mvs_fuse_depth_masked", _i, [_vp, _i, _i, _i32p, _i, _f, _f, _f, _i, _fp, C.POINTER(_i)]),
+    ("mvs_tsdf_integrate_masked", _i, [_vp, _i, _i32p, _i32p, _f, _i]),
+    ("mvs_fuse_sequence", _i, [_vp, _i, _i32p, _i, _i32p, _i, _f, _f, _f, _i, C.c_longlong, _fp, _i32p, C.POINTER(C.c_longlong)]),
+    ("mvs_fuse_sequence_points_device", _vp, [_vp]),
     ("mvs_depth_slot_matrices", _i, [_vp, _i, _fp]),
     ("mvs_tsdf_volume", _i, [_vp, _i, _fp, _f, _f]),
     ("mvs_tsdf_integrate", _i, [_vp, _i, _i32p, _f]),
@@ -625,7 +633,7 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
 
 
 def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coarse_planes, z_lo=-1.0, z_hi=1.0, cost=None, propagate=None,
-                        consistency=None, fetch=True):
+                        consistency=None, fetch=True, support=False):
     """Geometric propagation over frames of the frame store: main_slots [n] frame-store slots with their cameras
     main_cams [n,4,4]; side_slots [n,S] and side_cams [n,S,4,4] the side views of each.  The depth store must have 2 n slots
     (Context.depth_store); nothing else is allocated beyond what the calls below allocate.
@@ -635,6 +643,8 @@ def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coars
     device into depth slot i.
     Stage 2, for every main frame i: the term consistency=dict(weight=, max_px=) on the stage-1 slots of those of its side views that
     are main frames themselves, propagate_init from its own slot i, propagate_run; the z and cost maps go into slot n + i.
+    support=True: behind the upload of slot n + i its support map (how many of those neighbours confirm each pixel) goes device to device
+    into that slot's support plane (Context.depth_support_upload_device), for fuse_depth / fuse_sequence / tsdf_integrate with min_support.
     The term (and the gate) are off again on return -> the n stage-2 z maps [n,H,W] float32 (fetch=False: None, they are in the slots).
     WARNING: the neighbours' maps are estimated the same way as the map they correct: consistently wrong neighbours confirm each other,
     and the gain at depth steps is small (section 27 has the figures)."""
@@ -668,6 +678,8 @@ def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coars
                 if fetch:
                     out[i] = ctx.propagate_fetch()[0]
             ctx.depth_upload_device(stage * n + i, mc[i], ctx.propagate_depth_pointer(), ctx.propagate_cost_pointer())
+            if support and stage == 1:
+                ctx.depth_support_upload_device(n + i, ctx.propagate_support_pointer())
     return out
 
 
@@ -1077,20 +1089,88 @@ class Context:
         self._check(self.lib.mvs_depth_upload_device(self.h, int(slot), _ptr(c, _fp), C.c_void_p(int(depth_ptr)),
                                                      C.c_void_p(int(cost_ptr)) if cost_ptr else None))
 
-    def fuse_depth(self, ref_slot, neighbour_slots, min_consistent=2, max_reproj_px=1.0, max_rel_depth=0.01, max_cost=float("inf"), copy=True):
+    def depth_support_upload(self, slot, support):
+        """mvs_depth_support_upload: support [H,W] u8, the support plane of a filled depth slot (asynchronous: the array is kept alive here
+        until the next fuse_depth / fuse_sequence)"""
+        s = np.ascontiguousarray(np.asarray(support, dtype=np.uint8).reshape(self.H, self.W))
+        self.__dict__.setdefault("_depth_keep", {})[("support", int(slot))] = s
+        self._check(self.lib.mvs_depth_support_upload(self.h, int(slot), _ptr(s, _u8p)))
+
+    def depth_support_upload_device(self, slot, ptr):
+        """mvs_depth_support_upload_device: the device address of H*W u8, e.g. propagate_support_pointer() (stream-ordered)"""
+        self._check(self.lib.mvs_depth_support_upload_device(self.h, int(slot), C.c_void_p(int(ptr)) if ptr else None))
+
+    def depth_support_fetch(self, slot):
+        """mvs_depth_support_fetch -> (H, W) uint8, the slot's support plane; synchronises"""
+        out = np.empty((self.H, self.W), np.uint8)
+        self._check(self.lib.mvs_depth_support_fetch(self.h, int(slot), _ptr(out, _u8p)))
+        return out
+
+    def depth_support_drop(self, slot):
+        """mvs_depth_support_drop: the slot has no support plane any more (its depth map stays)"""
+        self._check(self.lib.mvs_depth_support_drop(self.h, int(slot)))
+
+    def fuse_depth(self, ref_slot, neighbour_slots, min_consistent=2, max_reproj_px=1.0, max_rel_depth=0.01, max_cost=float("inf"), copy=True,
+                   min_support=0):
         """mvs_fuse_depth -> (N, 7) float32 rows (x, y, z, 1, nx, ny, nz) in ascending pixel index.  copy=False: a view of the context's
-        reusable output buffer (the one process_frame uses), valid until the next call that writes it"""
+        reusable output buffer (the one process_frame uses), valid until the next call that writes it.  min_support > 0:
+        mvs_fuse_depth_masked, rule 1s on the slots' support planes"""
         nb = np.ascontiguousarray(np.asarray(list(neighbour_slots) if len(neighbour_slots) else [0], dtype=np.int32))
         if getattr(self, "_pf_out", None) is None:
             self._pf_out = np.zeros((self.H * self.W, 7), np.float32)
         out = self._pf_out
         n = C.c_int(0)
         try:
-            self._check(self.lib.mvs_fuse_depth(self.h, int(ref_slot), len(neighbour_slots), _ptr(nb, _i32p), int(min_consistent), float(max_reproj_px),
-                                                float(max_rel_depth), float(max_cost), _ptr(out, _fp), C.byref(n)))
+            if int(min_support):
+                self._check(self.lib.mvs_fuse_depth_masked(self.h, int(ref_slot), len(neighbour_slots), _ptr(nb, _i32p), int(min_consistent),
+                                                           float(max_reproj_px), float(max_rel_depth), float(max_cost), int(min_support), _ptr(out, _fp),
+                                                           C.byref(n)))
+            else:
+                self._check(self.lib.mvs_fuse_depth(self.h, int(ref_slot), len(neighbour_slots), _ptr(nb, _i32p), int(min_consistent), float(max_reproj_px),
+                                                    float(max_rel_depth), float(max_cost), _ptr(out, _fp), C.byref(n)))
         finally:
             self._depth_keep = {}
         return out[:n.value].copy() if copy else out[:n.value]
+
+    def fuse_sequence(self, ref_slots, neighbour_slots, min_consistent=2, max_reproj_px=1.0, max_rel_depth=0.01, max_cost=float("inf"), min_support=0,
+                      max_rows=None, copy=True):
+        """mvs_fuse_sequence -> (rows (N, 7) float32, ref_counts [nrefs] int32): the references fused in list order, every surface point
+        once.  neighbour_slots: one list per reference; ragged lists are padded with -1.  max_rows=None makes a
+        counting call first and then the exact one; otherwise at most max_rows rows come back (ref_counts and their sum are the totals
+        either way).  copy=False: the rows stay on the device (fuse_sequence_points_device()) and rows is None."""
+        refs = np.ascontiguousarray(np.asarray(list(ref_slots), dtype=np.int32).reshape(-1))
+        lists = [[int(s) for s in row] for row in neighbour_slots]
+        if len(lists) != len(refs):
+            raise ValueError("fuse_sequence: one neighbour list per reference")
+        K = max([len(row) for row in lists] + [0])
+        nb = np.full((max(len(refs), 1), max(K, 1)), -1, np.int32)
+        for i, row in enumerate(lists):
+            nb[i, :len(row)] = row
+        nb = np.ascontiguousarray(nb[:, :K]) if K else nb
+        counts = np.zeros(max(len(refs), 1), np.int32)
+        total = C.c_longlong(0)
+
+        def call(rows_max, out):
+            self._check(self.lib.mvs_fuse_sequence(self.h, len(refs), _ptr(refs, _i32p), K, _ptr(nb, _i32p), int(min_consistent), float(max_reproj_px),
+                                                   float(max_rel_depth), float(max_cost), int(min_support), int(rows_max),
+                                                   _ptr(out, _fp) if out is not None else None, _ptr(counts, _i32p), C.byref(total)))
+
+        try:
+            if max_rows is None:
+                call(0, None)
+                max_rows = total.value
+            out = np.zeros((min(int(max_rows), len(refs) * self.H * self.W), 7), np.float32) if copy and int(max_rows) > 0 else None
+            call(max_rows, out)
+        finally:
+            self._depth_keep = {}
+        if not copy:
+            return None, counts[:len(refs)].copy()
+        n = min(total.value, int(max_rows))
+        return (out[:n] if out is not None else np.zeros((0, 7), np.float32)), counts[:len(refs)].copy()
+
+    def fuse_sequence_points_device(self):
+        """device address of the rows of the last fuse_sequence (0 before the first)"""
+        return self.lib.mvs_fuse_sequence_points_device(self.h) or 0
 
     def fuse_points_device(self):
         """device address of the rows of the last fuse_depth (0 before the first)"""
@@ -1109,10 +1189,14 @@ class Context:
         self._check(self.lib.mvs_tsdf_volume(self.h, int(nodes_per_axis), _ptr(o, _fp), float(node_spacing), float(truncation)))
         self._tsdf_G = int(nodes_per_axis)
 
-    def tsdf_integrate(self, slots, max_cost=float("inf")):
-        """mvs_tsdf_integrate: add the listed depth-store slots' maps, in list order (asynchronous, stream-ordered)"""
+    def tsdf_integrate(self, slots, max_cost=float("inf"), min_support=0):
+        """mvs_tsdf_integrate: add the listed depth-store slots' maps, in list order (asynchronous, stream-ordered).  min_support > 0:
+        mvs_tsdf_integrate_masked, rule 1s on the slots' support planes"""
         sl = np.ascontiguousarray(np.asarray(list(slots) if len(slots) else [0], dtype=np.int32))
-        self._check(self.lib.mvs_tsdf_integrate(self.h, len(slots), _ptr(sl, _i32p), float(max_cost)))
+        if int(min_support):
+            self._check(self.lib.mvs_tsdf_integrate_masked(self.h, len(slots), _ptr(sl, _i32p), None, float(max_cost), int(min_support)))
+        else:
+            self._check(self.lib.mvs_tsdf_integrate(self.h, len(slots), _ptr(sl, _i32p), float(max_cost)))
 
     def tsdf_fetch(self):
         """mvs_tsdf_fetch -> (sum [G, G, G] f32, count [G, G, G] i32), indexed [k][j][i]"""
@@ -1182,14 +1266,17 @@ class Context:
         return self.lib.mvs_tsdf_raycast_depth_device(self.h) or 0, self.lib.mvs_tsdf_raycast_normals_device(self.h) or 0
 
     # ---- appearance of the TSDF volume --------------------------------------------------------------
-    def tsdf_integrate_frames(self, depth_slots, frame_slots, max_cost=float("inf")):
+    def tsdf_integrate_frames(self, depth_slots, frame_slots, max_cost=float("inf"), min_support=0):
         """mvs_tsdf_integrate_frames: mvs_tsdf_integrate of depth_slots, and frame-store slot frame_slots[e] votes its intensities into the
-        appearance volume along with depth_slots[e] (asynchronous, stream-ordered)"""
+        appearance volume along with depth_slots[e] (asynchronous, stream-ordered).  min_support > 0: mvs_tsdf_integrate_masked"""
         if len(depth_slots) != len(frame_slots):
             raise ValueError("depth_slots and frame_slots must pair up")
         ds = np.ascontiguousarray(np.asarray(list(depth_slots) if len(depth_slots) else [0], dtype=np.int32))
         fs = np.ascontiguousarray(np.asarray(list(frame_slots) if len(frame_slots) else [0], dtype=np.int32))
-        self._check(self.lib.mvs_tsdf_integrate_frames(self.h, len(depth_slots), _ptr(ds, _i32p), _ptr(fs, _i32p), float(max_cost)))
+        if int(min_support):
+            self._check(self.lib.mvs_tsdf_integrate_masked(self.h, len(depth_slots), _ptr(ds, _i32p), _ptr(fs, _i32p), float(max_cost), int(min_support)))
+        else:
+            self._check(self.lib.mvs_tsdf_integrate_frames(self.h, len(depth_slots), _ptr(ds, _i32p), _ptr(fs, _i32p), float(max_cost)))
 
     def tsdf_appearance_fetch(self):
         """mvs_tsdf_appearance_fetch -> cells [G, G, G] u32 (count << 24 | sum), indexed [k][j][i]"""
