@@ -21,7 +21,7 @@ struct Hooks {
     bool debug_flags = false;          // MVS_DEBUG_FLAGS=1: bits 8-23 of mvs_sweep_run's flags (timing experiments, forced splits) are honoured
     bool no_rect = false;              // MVS_NO_RECT=1: never plan the rectified-view kernels
     bool no_plan_cache = false;        // MVS_NO_PLAN_CACHE=1: initial state of mvs_sweep_set_plan_cache (0 = plan every view set)
-    std::string plan_dump;             // MVS_PLAN_DUMP=<file>: plan_regions_fx writes its descriptors there (tools/plan_hist.py)
+    std::string plan_dump;             // MVS_PLAN_DUMP=<file>: plan_regions_fx and plan_regions write their descriptors there (tools/plan_hist.py, tests/sweep_cameras.py)
     bool rect_verbose = false;         // MVS_RECT_VERBOSE=1: box sizes of the rectified planners on stderr
     // ---- other stages ----
     bool filter_timing = false;        // MVS_FILTER_TIMING=1: stage timer of mvs_filter_points on stderr

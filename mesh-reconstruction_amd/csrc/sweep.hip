@@ -22,7 +22,9 @@
 //   sweep_generic     no tiling, global gathers; any geometry; also the in-kernel fallback
 #include "sweep_shared.hpp"
 
+#include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 namespace mvs {
 
@@ -780,7 +782,7 @@ static int sweep_run_exact(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &
         return MVS_OK;
     }
     if ((rc = ensure_pads(ctx))) return rc;  // sweep_tiled's generic regions and the un-tiled kernel gather single texels of the padded frames
-    if (ctx->exact_tiled_planned && ctx->plan_forced != force_tall) ctx->exact_tiled_planned = false;
+    if (ctx->exact_tiled_planned && (ctx->plan_forced != force_tall || !ctx->hooks.plan_dump.empty())) ctx->exact_tiled_planned = false;  // (MVS_PLAN_DUMP: no plan is reused, as on the fixed path)
     if (!f.generic && !ctx->exact_tiled_planned && ctx->V > 0) {
         ctx->snap_valid = false;  // ctx->plan is about to hold the exact sampler's regions
         if ((rc = ensure(ctx, ctx->plan_stats, 64))) return rc;
@@ -802,6 +804,20 @@ static int sweep_run_exact(mvs_ctx *ctx, const SweepRange &r, const SweepFlags &
             MVS_HIP(ctx, hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
             MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
             if ((long long)h[0] * 50 <= (long long)h[1]) break;  // at most 2 % oversize: keep 2 x 32
+        }
+        if (!ctx->hooks.plan_dump.empty()) {  // diagnostic, the format of the fixed path's dump: header {tiles_x, tiles_y, nchunks, V}, then the descriptors of the shape that is kept
+            SweepParams q;
+            fill_params(ctx, q, 0, ctx->V, ctx->plan_shape == 1 ? 8 : 16, ctx->plan_shape == 1 ? 32 : 16);
+            const size_t n = (size_t)q.tiles_x * q.tiles_y * q.nchunks * q.V;
+            std::vector<uint2> host(n);
+            MVS_HIP(ctx, hipMemcpyAsync(host.data(), ctx->plan.ptr, n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+            MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (FILE *fp = fopen(ctx->hooks.plan_dump.c_str(), "wb")) {
+                const int hdr[4] = {q.tiles_x, q.tiles_y, q.nchunks, q.V};
+                fwrite(hdr, sizeof(int), 4, fp);
+                fwrite(host.data(), sizeof(uint2), n, fp);
+                fclose(fp);
+            }
         }
         ctx->exact_tiled_planned = true;
         ctx->plan_forced = force_tall;
