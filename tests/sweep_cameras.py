@@ -10,7 +10,8 @@ and with D = 16 the planes are z_d = (2 d - 15) / 16.
 
 Each case carries `premise(case, m)`, a check over the mirror's numbers that the case is what it is there for (m: the dictionary of
 `mirror_of`), and `plan_premise(case, plan)`, the same over the planner's descriptors of the device (`read_plan` of an MVS_PLAN_DUMP file).
-Importable by the windowed sweeps' tests as well; it has no cases for them."""
+tests/window_cameras.py reuses the ladders, shear_tie, horizon, axial, checker_extreme, skip_then_border, one_plane and ragged_shear for
+the windowed sweeps, the band sweeps and the propagation, with premises of its own over the windows, and adds the cases those kernels need."""
 import functools
 from fractions import Fraction
 

@@ -8,7 +8,8 @@ oracle/sweep_oracle.c, and calling nothing of the oracle.  Every rounding the co
                  and its fraction, so the tie is decided on exact numbers;
   * c, i, a, res the exact sampler's float32 chain of section 2a, one rounding per operation.
 
-Volumes are [D, H, W] uint32, cells count << 24 | sum (fixed) resp. count << 16 | sum (exact).  `exact_u` is the scalar, exact-rational
+`project` and `sample_fixed` take the planes as the table [D] or as a per-pixel map [D, H, W] (the band sweeps and the windowed kernels'
+cases, tests/window_cameras.py).  Volumes are [D, H, W] uint32, cells count << 24 | sum (fixed) resp. count << 16 | sum (exact).  `exact_u` is the scalar, exact-rational
 form of u before its rounding (fractions.Fraction), for the premises of crafted cases."""
 from fractions import Fraction
 
@@ -53,9 +54,11 @@ def pixel_ndc(W, H):
 
 
 def project(Q, z, W, H):
-    """s = fma(z, B, A) for one view: three [D, H, W] float32 arrays (x, y, w)"""
+    """s = fma(z, B, A) for one view: three [D, H, W] float32 arrays (x, y, w).  z is the plane table [D] or a per-pixel plane map
+    [D, H, W]: every pixel of plane d at its own depth (the band sweeps)"""
     Q = np.asarray(Q, F).reshape(3, 4)
     z = np.asarray(z, F)
+    assert z.ndim == 1 or z.shape[1:] == (H, W), z.shape
     xn, yn = pixel_ndc(W, H)
     xn = np.broadcast_to(xn[None, :], (H, W)).copy()
     yn = np.broadcast_to(yn[:, None], (H, W)).copy()
@@ -63,7 +66,7 @@ def project(Q, z, W, H):
     for k in range(3):
         full = lambda v: np.full((H, W), v, F)
         A = _fma32(full(Q[k, 0]), xn, _fma32(full(Q[k, 1]), yn, full(Q[k, 3])))
-        zz = np.broadcast_to(z[:, None, None], (len(z), H, W)).copy()
+        zz = np.broadcast_to(z[:, None, None] if z.ndim == 1 else z, (len(z), H, W)).copy()
         out.append(_fma32(zz, np.full_like(zz, Q[k, 2]), np.broadcast_to(A[None], zz.shape).copy()))
     return out
 
@@ -98,10 +101,14 @@ def rne_u(s, r):
 
 
 def sample_fixed(Q, z, pad, W, H, table=None):
-    """section 2b for one view -> dict(valid, dot, ux, uy, tie, kx, ky), [D, H, W] each"""
+    """section 2b for one view -> dict(valid, dot, ux, uy, tie, kx, ky), [D, H, W] each; z as in `project`.  A sample at a z that is
+    not finite (a per-pixel map's dead plane) is not valid"""
     table = weight_table() if table is None else table
-    sx, sy, sw = project(Q, z, W, H)
+    z = np.asarray(z, F)
+    finite = np.isfinite(z)
+    sx, sy, sw = project(Q, np.where(finite, z, F(0)), W, H)        # (the dead samples are projected at z = 0 and dropped below)
     front, r = reciprocal(sw)
+    front = front & np.broadcast_to(finite[:, None, None] if z.ndim == 1 else finite, front.shape)
     ux, tx = rne_u(sx, r)
     uy, ty = rne_u(sy, r)
     valid = front & (ux > 132) & (ux < 256 * W + 132) & (uy > 132) & (uy < 256 * H + 132)
