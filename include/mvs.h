@@ -438,7 +438,7 @@ int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, 
  * Errors: those of mvs_sweep_run_bestk, and MVS_EINVAL for radius 0 and for tau outside 0..255.  Every check comes before the first
  * allocation; after an error nothing is written and the context stays usable. */
 int mvs_sweep_run_bestk_gated(mvs_ctx *ctx, int view_first, int view_count, int cost, int radius, int keep, int tau, const void *guide_dev, unsigned flags);
-/* Band sweep with windowed costs: mvs_sweep_run_bestk with plane d of pixel q at prior(q) + delta_d (csrc/band_bestk.hip; DESIGN.md
+/* Band sweep with windowed costs: mvs_sweep_run_bestk with plane d of pixel q at prior(q) + delta_d (csrc/bestk.hip; DESIGN.md
  * section 24 is the contract; bit-identical to tests/band_bestk_mirror.py).  Fixed sampler only.  It joins the band sweep's planes, spent
  * where a prior says the surface is, with the matching costs that survive exposure drift (ZNCC) and occlusion (best-K), so that the
  * coarse-to-fine paths can run on frames on which the absolute difference fails.  MVS_COST_ZNCC with MVS_KEEP_ALL is the ZNCC band sweep.

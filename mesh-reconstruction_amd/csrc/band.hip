@@ -11,7 +11,8 @@
 // one pixel per thread; a wavefront covers 2 rows x 32 columns, so a plane's volume store is two full 128-byte segments.  The 4 KiB weight
 // table sits in LDS (the kernel's only LDS); the texel quad is ONE dword of the view's quad image, read without a branch: a sample that is
 // out of frame or on a dead plane reads quad 0 and is dropped by a select.  A dead plane (no prior, or prior + delta outside (-1, 1))
-// carries z = NaN, which fails the sampler's own s.w > 0 test, so it costs no mask register.
+// carries z = NaN, which fails the sampler's own s.w > 0 test, so it costs no mask register.  The sample is absdiff_sample
+// (sweep_shared.hpp), the one the windowed sweeps take: its e | ok << 24 is this sweep's cell of one view.
 #include "sweep_shared.hpp"
 
 #include <climits>
@@ -24,22 +25,6 @@ namespace {
 
 constexpr int BAND_TW = 32, BAND_TH = 8;   // pixels per tile: 256 threads
 constexpr int BAND_PC = 16;                // planes per accumulator chunk
-constexpr float BAND_MAGIC = 12582912.0f;  // 1.5 * 2^23, as sweep_fx.hip's FX_MAGIC
-
-__device__ __forceinline__ uint32_t band_sample(const Affine &A, float bx, float by, float bw, float z, const uint32_t *__restrict__ quads, uint32_t pitch, float hix,
-                                                float hiy, const uint32_t *__restrict__ lut, uint32_t Im255)
-{
-    const float sx = __builtin_fmaf(z, bx, A.ax), sy = __builtin_fmaf(z, by, A.ay), sw = __builtin_fmaf(z, bw, A.aw);
-    const float r256 = rcp_rn(sw) * 256.0f;
-    const float tx = __builtin_fmaf(sx, r256, BAND_MAGIC + 4.0f), ty = __builtin_fmaf(sy, r256, BAND_MAGIC + 4.0f);
-    const bool ok = sw > 0.0f && tx > BAND_MAGIC + 132.0f && tx < hix && ty > BAND_MAGIC + 132.0f && ty < hiy;  // false for z = NaN
-    const uint32_t ux = __builtin_bit_cast(uint32_t, tx) & 0x3fffffu, uy = __builtin_bit_cast(uint32_t, ty) & 0x3fffffu;  // t - magic
-    const uint32_t quad = quads[ok ? (uy >> 8) * pitch + (ux >> 8) : 0u];   // in frame: column <= W, row <= H of the (H + 2) x pitch quad image
-    const uint32_t w = lut[(((uy >> 3) & 31u) << 5) | ((ux >> 3) & 31u)];
-    // (the builtin, not inline asm: sweep_fx.hip, sad_u16)
-    const uint32_t cell = __builtin_amdgcn_sad_u16(__builtin_amdgcn_udot4(quad, w, 0u, false), Im255, 1u << 24);
-    return ok ? cell : 0u;
-}
 
 // one chunk of up to BAND_PC planes from d0: the cells of the listed views into acc.  TAIL: the chunk has n < BAND_PC planes
 template <bool TAIL>
@@ -59,7 +44,7 @@ __device__ __forceinline__ void band_chunk(const SweepParams &p, const uint32_t 
         const uint32_t *qv = p.quads + p.pad_slab * (size_t)(p.view_slot ? p.view_slot[v] : v);
 #pragma unroll
         for (int k = 0; k < BAND_PC; k++)
-            if (!TAIL || k < n) acc[k] += band_sample(A, q[2], q[6], q[10], zc[k], qv, (uint32_t)p.pitch, hix, hiy, lut, Im255);
+            if (!TAIL || k < n) acc[k] += absdiff_sample(A, q[2], q[6], q[10], zc[k], qv, (uint32_t)p.pitch, hix, hiy, lut, Im255);
     }
 }
 
@@ -78,7 +63,7 @@ __global__ __launch_bounds__(256) void sweep_fx_band(SweepParams p, const uint32
     const float xn = __builtin_fmaf((float)(2 * col + 1), p.invW, -1.0f);
     const float yn = __builtin_fmaf(-(float)(2 * row + 1), p.invH, 1.0f);
     const uint32_t Im255 = 255u * p.main_img[pix];
-    const float hix = BAND_MAGIC + 132.0f + 256.0f * (float)p.W, hiy = BAND_MAGIC + 132.0f + 256.0f * (float)p.H;
+    const float hix = ZN_MAGIC + 132.0f + 256.0f * (float)p.W, hiy = ZN_MAGIC + 132.0f + 256.0f * (float)p.H;
     const float z0 = prior[pix];
     const bool has = z0 > -1.0f && z0 < 1.0f;   // rule 1 (false for NaN)
     uint32_t best = 0;

@@ -4,21 +4,43 @@
 // A view that cannot see the surface point of a (pixel, plane), because a nearer surface hides it, adds a wrong cost to the summing
 // sweeps' cell.  Here the per-view costs c_v of the counted views are merged as k << 24 | (the sum of the k smallest), k = min(keep,
 // counted views): the views that disagree most are left out.  The cost of a view is windowed (best-K of single-pixel costs picks texture
-// aliasing): either the ZNCC cost of zncc.hip, rules 1-4 unchanged, or the mean of |dot - 255 I_main| over the window's members in integer
+// aliasing): either the ZNCC cost of section 21, rules 1-4 unchanged, or the mean of |dot - 255 I_main| over the window's members in integer
 // division.  The volume is the packed volume of the ordinary sweep, so everything behind it runs unchanged.
 //
-// sweep_fx_bestk<COST, R, KMAX> is sweep_fx_zncc's skeleton: a 32 x 16-pixel tile, 256 threads, two pixels per thread, tile + halo sampled
-// once per (plane, view) into LDS, a separable window sum (horizontal pass, barrier, vertical pass), a chunk of ZN_PC planes in registers.
-//   The window element: ZNCC's 16-byte element as it is (sweep_shared.hpp); for the absolute difference ONE dword e | ok << 24, so that
-//     the window sum is N << 24 | S with plain adds (N <= 81 < 2^7, S <= 81 * 65025 < 2^23): a quarter of the LDS and ds_read_b32.
-//     Radius 0 of the absolute difference has no window: the thread's two samples ARE its two pixels, no LDS pass and no barrier.
-//   The merge: where sweep_fx_zncc adds the view's cell, this kernel keeps the KMAX smallest costs of each (pixel, plane) of the chunk in
-//     registers, sorted by a branch-free insertion chain (v_min_u32 / v_max_u32 per slot); a view that does not count carries 0xffffffff,
-//     which sinks to the end.  The chunk's epilogue counts and sums the first `keep` slots below the sentinel.  The sum of the k smallest
-//     values does not depend on how equal values are ordered, so there is no tie rule.  KMAX = 0 is MVS_KEEP_ALL: a plain accumulator.
-//   Instantiations: (4 radii of ZNCC + 5 of the absolute difference) x KMAX in {0, 2, 4, 8} = 36; `keep` (<= KMAX) and the two outputs are
-//     kernel arguments, uniform branches in the chunk's epilogue, not template parameters (x 3 would be 108 kernels for nothing measurable).
-#include "bestk_rules.hpp"   // BkCost, BkList, absdiff_sample: shared with band_bestk.hip
+// The same cell on the band sweep's planes (mvs_sweep_run_band_bestk; DESIGN.md section 24 is the contract, tests/band_bestk_mirror.py
+// states it): plane d of pixel q is  z_d(q) = prior(q) + delta_d  with delta the context's plane table, and window member q is sampled at
+// ITS OWN pixel's plane z_d(q), not at z_d(p), so the window follows the prior surface (a slanted support window where the prior is
+// smooth).  The state afterwards is the band state (band.hip).  MVS_COST_ZNCC with MVS_KEEP_ALL writes the cells of the ZNCC sweep
+// (zncc.hip keeps a kernel of its own: this one was 1-7 % slower there) or is the ZNCC band sweep.
+//
+// sweep_fx_bestk<COST, R, KMAX, BAND>, sweep_fx_zncc's skeleton: a workgroup is a 32 x 16-pixel tile, 256 threads, two
+// pixels per thread (rows ty and ty + 8 of the tile).  Per (plane, view) the threads sample tile + halo once, (32 + 2R)(16 + 2R) samples,
+// band.hip's un-tiled sample with one dword gather per quad and the weight table in LDS, into one LDS element each; the window sum is
+// separable with plain adds and no unpacking: a horizontal pass ((16 + 2R) x 32 outputs of 2R + 1 reads), a barrier, a vertical pass
+// (2R + 1 reads per pixel); a wavefront reads 64 consecutive elements, which is conflict free.  Two barriers per (plane, view): samples ->
+// row sums -> pixels; the next iteration's sample writes come behind the second barrier and its row-sum writes behind its own first, so
+// neither buffer is doubled.  Barriers are hidden by the other workgroups of the CU, not by a pipeline inside the workgroup.  The view's
+// affine part of the thread's sample positions is amortised over a chunk of ZN_PC planes, whose cells live in registers until the
+// chunk's epilogue.
+//   The window element: ZNCC's 16-byte element (sweep_shared.hpp: zncc_sample; LDS: 4 KiB table + 16 B (HH HW + 32 HH) = 22.6 / 25.3 /
+//     28.1 / 31.0 KiB at R = 1 .. 4); for the absolute difference ONE dword e | ok << 24, so that the window sum is N << 24 | S with plain
+//     adds (N <= 81 < 2^7, S <= 81 * 65025 < 2^23): a quarter of the LDS and ds_read_b32.  Radius 0 of the absolute difference has no
+//     window: the thread's two samples ARE its two pixels, no LDS pass and no barrier.
+//   The merge: the kernel keeps the KMAX smallest costs of each (pixel, plane) of the chunk in registers, sorted by a branch-free
+//     insertion chain (v_min_u32 / v_max_u32 per slot); a view that does not count carries 0xffffffff, which sinks to the end.  The
+//     chunk's epilogue counts and sums the first `keep` slots below the sentinel.  The sum of the k smallest values does not depend on
+//     how equal values are ordered, so there is no tie rule.  KMAX = 0 is MVS_KEEP_ALL: a plain accumulator that adds the view's cell.
+//   BAND: each of the thread's sample positions loads its prior once, and the z of a sample is prior + delta_d, or NaN for a dead plane
+//     (no prior, or the sum outside (-1, 1)); the sampler's own s.w > 0 test rejects NaN, as in band.hip, so there is no second mask.  A
+//     position outside the frame carries NaN already.  The add and the range test are done per (view, plane, sample), not once per
+//     chunk: a chunk's planes kept in NS x ZN_PC registers cost a wave per SIMD in most instantiations and, where they did, 7 % at
+//     1080p x 16 views.  Without BAND `prior` is unused and every sample of a plane has the table's z.
+//   Instantiations: (4 radii of ZNCC + 5 of the absolute difference) x KMAX in {0, 2, 4, 8} x BAND = 72; `keep` (<= KMAX) and the two
+//     outputs are kernel arguments, uniform branches in the chunk's epilogue, not template parameters (x 3 would be 216 kernels for
+//     nothing measurable).
+//   The body stays inside the one __global__ template: a thin kernel per sweep around a __forceinline__ body cost 6 vector registers and
+//     a wave per SIMD in most instantiations.
+#include "bestk_rules.hpp"   // BkCost, BkList, with_bestk_shape
 
 namespace mvs {
 
@@ -26,8 +48,9 @@ int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the 32 x 32 weight table on t
 
 namespace {
 
-template <int COST, int R, int KMAX>
-__global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, const uint32_t *__restrict__ lut_g, int keep, int write_volume, int fused)
+template <int COST, int R, int KMAX, bool BAND>
+__global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, const uint32_t *__restrict__ lut_g, const float *__restrict__ prior, int keep, int write_volume,
+                                                              int fused)
 {
     using S = ZnShape<R>;
     using C = BkCost<COST>;
@@ -42,8 +65,8 @@ __global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, cons
     for (int i = 0; i < 4; i++) lut[tid + ZN_THREADS * i] = lut_g[tid + ZN_THREADS * i];
     __syncthreads();
     const int x0 = blockIdx.x * ZN_TW, y0 = blockIdx.y * ZN_TH;
-    // this thread's sample positions: elements tid + 256 s of tile + halo (R = 0: its own two pixels)
-    float sxn[S::NS], syn[S::NS];
+    // this thread's sample positions: elements tid + 256 s of tile + halo (R = 0: its own two pixels); BAND: each with its own prior
+    float sxn[S::NS], syn[S::NS], sz0[BAND ? S::NS : 1];
     uint32_t sa[S::NS], saa[S::NS];   // ZNCC: a, a a; absolute difference: 255 a, unused
 #pragma unroll
     for (int s = 0; s < S::NS; s++) {
@@ -51,11 +74,16 @@ __global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, cons
         const int hy = i / S::HW, hx = i - hy * S::HW;
         const int col = x0 - R + hx, row = y0 - R + hy;
         const bool live = i < S::SAMPLES && col >= 0 && col < p.W && row >= 0 && row < p.H;   // pixels outside the frame are no members
-        const uint32_t a = live ? (uint32_t)p.main_img[(size_t)row * p.W + col] : 0u;
+        const size_t at = live ? (size_t)row * p.W + col : 0;
+        const uint32_t a = live ? (uint32_t)p.main_img[at] : 0u;
         sa[s] = ZNCC ? a : 255u * a;
         saa[s] = a * a;
         sxn[s] = live ? __builtin_fmaf((float)(2 * col + 1), p.invW, -1.0f) : __builtin_nanf("");
         syn[s] = __builtin_fmaf(-(float)(2 * row + 1), p.invH, 1.0f);
+        if constexpr (BAND) {
+            const float z0 = prior[at];
+            sz0[s] = (live && z0 > -1.0f && z0 < 1.0f) ? z0 : __builtin_nanf("");   // section 19 rule 1 (false for NaN)
+        }
     }
     const int c = tid & (ZN_TW - 1), ty = tid / ZN_TW;   // pixels (c, ty) and (c, ty + 8) of the tile
     const int col = x0 + c;
@@ -80,12 +108,22 @@ __global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, cons
 #pragma unroll
             for (int k = 0; k < ZN_PC; k++) {
                 if (k >= n) break;
-                const float z = p.z[d0 + k];
+                const float zk = p.z[d0 + k];   // BAND: the offset delta_d
+                float zs[S::NS];                // the plane of every sample position; BAND: NaN where it is dead
+#pragma unroll
+                for (int s = 0; s < S::NS; s++) {
+                    if constexpr (BAND) {
+                        const float z = sz0[s] + zk;   // one add (section 19 rule 2)
+                        zs[s] = (z > -1.0f && z < 1.0f) ? z : __builtin_nanf("");
+                    } else {
+                        zs[s] = zk;
+                    }
+                }
                 if constexpr (!WINDOW) {
                     // c = e(p): sample s is pixel (c, ty + 8 s)
 #pragma unroll
                     for (int h = 0; h < 2; h++) {
-                        const uint32_t e = absdiff_sample(A[h], q[2], q[6], q[10], z, qv, (uint32_t)p.pitch, hix, hiy, lut, sa[h]);
+                        const uint32_t e = absdiff_sample(A[h], q[2], q[6], q[10], zs[h], qv, (uint32_t)p.pitch, hix, hiy, lut, sa[h]);
                         acc[h][k].insert(e ? e & 0xffffffu : BK_NONE);
                     }
                 } else {
@@ -94,9 +132,9 @@ __global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, cons
                         const int i = tid + ZN_THREADS * s;
                         Elem e;
                         if constexpr (ZNCC)
-                            e = zncc_sample(A[s], q[2], q[6], q[10], z, qv, (uint32_t)p.pitch, hix, hiy, lut, sa[s], saa[s]);
+                            e = zncc_sample(A[s], q[2], q[6], q[10], zs[s], qv, (uint32_t)p.pitch, hix, hiy, lut, sa[s], saa[s]);
                         else
-                            e = absdiff_sample(A[s], q[2], q[6], q[10], z, qv, (uint32_t)p.pitch, hix, hiy, lut, sa[s]);
+                            e = absdiff_sample(A[s], q[2], q[6], q[10], zs[s], qv, (uint32_t)p.pitch, hix, hiy, lut, sa[s]);
                         if (i < S::SAMPLES) smp[i] = e;
                     }
                     __syncthreads();
@@ -144,38 +182,33 @@ __global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, cons
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const int row = y0 + ty + 8 * h;
-            if (col < p.W && row < p.H) store_best<CS_FIXED>(p, (size_t)row * p.W + col, best[h] & 0xffffffu, best[h] >> 24, bi[h]);
+            if (col < p.W && row < p.H) store_best<CS_FIXED>(p, (size_t)row * p.W + col, best[h] & 0xffffffu, best[h] >> 24, bi[h]);   // BAND: depth = delta[index], an offset
         }
     }
 }
 
-template <int COST, int R>
-void bestk_launch(mvs_ctx *ctx, const SweepParams &p, int keep, bool vol, bool fused)
+// what the two entries refuse alike
+int bestk_arguments(mvs_ctx *ctx, const char *who, int cost, int radius, int keep)
+{
+    if (cost != MVS_COST_ABSDIFF && cost != MVS_COST_ZNCC) return fail(ctx, MVS_EINVAL, "%s: unknown cost %d", who, cost);
+    const int rmin = cost == MVS_COST_ZNCC ? 1 : 0;
+    if (radius < rmin || radius > 4) return fail(ctx, MVS_EINVAL, "%s: radius %d outside %d..4", who, radius, rmin);
+    if (keep < 0 || keep > 8) return fail(ctx, MVS_EINVAL, "%s: keep %d outside 1..8 and not MVS_KEEP_ALL", who, keep);
+    return MVS_OK;
+}
+
+// the launch for checked (cost, radius, keep); `prior` non-null: the band's planes prior + delta
+void bestk_tile_launch(mvs_ctx *ctx, const SweepParams &p, const float *prior, int cost, int radius, int keep, bool vol, bool fused)
 {
     const dim3 grid((unsigned)div_up(ctx->W, ZN_TW), (unsigned)div_up(ctx->H, ZN_TH));
     const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
-    if (keep == MVS_KEEP_ALL)
-        sweep_fx_bestk<COST, R, 0><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, keep, vol, fused);
-    else if (keep <= 2)
-        sweep_fx_bestk<COST, R, 2><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, keep, vol, fused);
-    else if (keep <= 4)
-        sweep_fx_bestk<COST, R, 4><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, keep, vol, fused);
-    else
-        sweep_fx_bestk<COST, R, 8><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, keep, vol, fused);
-}
-
-template <int COST>
-void bestk_launch_radius(mvs_ctx *ctx, const SweepParams &p, int radius, int keep, bool vol, bool fused)
-{
-    switch (radius) {
-    case 0:
-        if constexpr (COST == MVS_COST_ABSDIFF) bestk_launch<COST, 0>(ctx, p, keep, vol, fused);   // (refused for ZNCC by the caller)
-        break;
-    case 1: bestk_launch<COST, 1>(ctx, p, keep, vol, fused); break;
-    case 2: bestk_launch<COST, 2>(ctx, p, keep, vol, fused); break;
-    case 3: bestk_launch<COST, 3>(ctx, p, keep, vol, fused); break;
-    default: bestk_launch<COST, 4>(ctx, p, keep, vol, fused); break;
-    }
+    with_bestk_shape<0>(cost, radius, keep, [&](auto c, auto r, auto kmax) {
+        constexpr int COST = decltype(c)::value, R = decltype(r)::value, KMAX = decltype(kmax)::value;
+        if (prior)
+            sweep_fx_bestk<COST, R, KMAX, true><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, prior, keep, vol, fused);
+        else
+            sweep_fx_bestk<COST, R, KMAX, false><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, prior, keep, vol, fused);
+    });
 }
 
 }  // namespace
@@ -186,28 +219,55 @@ using namespace mvs;
 
 int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, int radius, int keep, unsigned flags)
 {
-    if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_sweep_run_bestk: null context");
-    if (cost != MVS_COST_ABSDIFF && cost != MVS_COST_ZNCC) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_bestk: unknown cost %d", cost);
-    const int rmin = cost == MVS_COST_ZNCC ? 1 : 0;
-    if (radius < rmin || radius > 4) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_bestk: radius %d outside %d..4", radius, rmin);
-    if (keep < 0 || keep > 8) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_bestk: keep %d outside 1..8 and not MVS_KEEP_ALL", keep);
+    static const char who[] = "mvs_sweep_run_bestk";
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
     bool vol, fused;
     int rc;
-    if ((rc = fx_sweep_preconditions(ctx, "mvs_sweep_run_bestk", view_first, view_count, flags, vol, fused))) return rc;
+    if ((rc = bestk_arguments(ctx, who, cost, radius, keep))) return rc;
+    if ((rc = fx_sweep_preconditions(ctx, who, view_first, view_count, flags, vol, fused))) return rc;
     MVS_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = sweep_outputs(ctx, vol, "mvs_sweep_run_bestk"))) return rc;
+    if ((rc = sweep_outputs(ctx, vol, who))) return rc;
     if ((rc = ensure_fx_lut(ctx))) return rc;
     SweepParams p;
     fill_params(ctx, p, view_first, view_count, ZN_TH, ZN_PC);
     {
         ProfileScope ps(ctx, MVS_K_SWEEP);
-        if (cost == MVS_COST_ZNCC)
-            bestk_launch_radius<MVS_COST_ZNCC>(ctx, p, radius, keep, vol, fused);
-        else
-            bestk_launch_radius<MVS_COST_ABSDIFF>(ctx, p, radius, keep, vol, fused);
+        bestk_tile_launch(ctx, p, nullptr, cost, radius, keep, vol, fused);
     }
     MVS_HIP(ctx, hipGetLastError());
     note_ordinary_sweep(ctx);
+    fused ? note_full_selection(ctx) : note_no_selection(ctx);
+    return MVS_OK;
+}
+
+int mvs_sweep_run_band_bestk(mvs_ctx *ctx, int view_first, int view_count, const void *prior_dev, int cost, int radius, int keep, unsigned flags)
+{
+    static const char who[] = "mvs_sweep_run_band_bestk";
+    if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
+    if (!prior_dev) return fail(ctx, MVS_EINVAL, "%s: prior_dev is null", who);
+    bool vol, fused;
+    int rc;
+    if ((rc = bestk_arguments(ctx, who, cost, radius, keep))) return rc;
+    if ((rc = fx_sweep_preconditions(ctx, who, view_first, view_count, flags, vol, fused))) return rc;
+    for (int d = 0; d < ctx->D; d++)
+        if (!(ctx->z_host[d] > -1.0f && ctx->z_host[d] < 1.0f))
+            return fail(ctx, MVS_ESTATE, "%s: the plane table holds the band's offsets and must lie inside (-1, 1): offset %d is %g", who, d, ctx->z_host[d]);
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)ctx->W * ctx->H;
+    if ((rc = sweep_outputs(ctx, vol, who))) return rc;
+    if ((rc = ensure(ctx, ctx->band_prior, P * sizeof(float)))) return rc;
+    if ((rc = ensure_fx_lut(ctx))) return rc;
+    // the context's own copy: the caller's map may be the depth map this run overwrites (stream order puts the copy first)
+    if (prior_dev != ctx->band_prior.ptr) MVS_HIP(ctx, hipMemcpyAsync(ctx->band_prior.ptr, prior_dev, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    SweepParams p;
+    fill_params(ctx, p, view_first, view_count, ZN_TH, ZN_PC);
+    {
+        ProfileScope ps(ctx, MVS_K_SWEEP);
+        bestk_tile_launch(ctx, p, (const float *)ctx->band_prior.ptr, cost, radius, keep, vol, fused);
+    }
+    MVS_HIP(ctx, hipGetLastError());
+    ctx->band_planes = ctx->D;   // the band state, exactly as mvs_sweep_run_band leaves it
+    ctx->band_resolved = false;
     fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }

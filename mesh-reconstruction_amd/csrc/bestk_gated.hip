@@ -16,7 +16,7 @@
 //     rolled for the same reason): unrolled, every mask of both pixels is invariant in the plane and view loops and is hoisted out of
 //     them, 2 x 81 registers at radius 4 (window.hip met the same with 8 x 81 and spilled).
 //   Instantiations: 2 costs x 4 radii x KMAX in {0, 2, 4, 8} = 32.  Radius 0 has no window to gate and is refused.
-#include "bestk_rules.hpp"   // BkCost, BkList, absdiff_sample: shared with bestk.hip and band_bestk.hip
+#include "bestk_rules.hpp"   // BkCost, BkList, with_bestk_shape: shared with bestk.hip and propagate.hip
 
 namespace mvs {
 
@@ -175,32 +175,6 @@ struct GateArgs {
     bool vol, fused;
 };
 
-template <int COST, int R>
-void gated_launch(mvs_ctx *ctx, const SweepParams &p, const GateArgs &g)
-{
-    const dim3 grid((unsigned)div_up(ctx->W, ZN_TW), (unsigned)div_up(ctx->H, ZN_TH));
-    const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
-    if (g.keep == MVS_KEEP_ALL)
-        sweep_fx_bestk_gated<COST, R, 0><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, g.guide, g.tau, g.keep, g.vol, g.fused);
-    else if (g.keep <= 2)
-        sweep_fx_bestk_gated<COST, R, 2><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, g.guide, g.tau, g.keep, g.vol, g.fused);
-    else if (g.keep <= 4)
-        sweep_fx_bestk_gated<COST, R, 4><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, g.guide, g.tau, g.keep, g.vol, g.fused);
-    else
-        sweep_fx_bestk_gated<COST, R, 8><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, g.guide, g.tau, g.keep, g.vol, g.fused);
-}
-
-template <int COST>
-void gated_launch_radius(mvs_ctx *ctx, const SweepParams &p, int radius, const GateArgs &g)
-{
-    switch (radius) {
-    case 1: gated_launch<COST, 1>(ctx, p, g); break;
-    case 2: gated_launch<COST, 2>(ctx, p, g); break;
-    case 3: gated_launch<COST, 3>(ctx, p, g); break;
-    default: gated_launch<COST, 4>(ctx, p, g); break;
-    }
-}
-
 }  // namespace
 
 }  // namespace mvs
@@ -228,10 +202,11 @@ int mvs_sweep_run_bestk_gated(mvs_ctx *ctx, int view_first, int view_count, int 
     g.keep = keep;
     {
         ProfileScope ps(ctx, MVS_K_SWEEP);
-        if (cost == MVS_COST_ZNCC)
-            gated_launch_radius<MVS_COST_ZNCC>(ctx, p, radius, g);
-        else
-            gated_launch_radius<MVS_COST_ABSDIFF>(ctx, p, radius, g);
+        const dim3 grid((unsigned)div_up(ctx->W, ZN_TW), (unsigned)div_up(ctx->H, ZN_TH));
+        const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
+        with_bestk_shape<1>(cost, radius, keep, [&](auto c, auto r, auto kmax) {
+            sweep_fx_bestk_gated<decltype(c)::value, decltype(r)::value, decltype(kmax)::value><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, g.guide, g.tau, g.keep, g.vol, g.fused);
+        });
     }
     MVS_HIP(ctx, hipGetLastError());
     note_ordinary_sweep(ctx);

@@ -1,29 +1,13 @@
-// bestk_rules.hpp -- what the two best-K sweeps (bestk.hip: the global plane table; band_bestk.hip: planes in a band around a per-pixel
-// prior) have in common on the device: the absolute difference's window element, a cost's window arithmetic (BkCost) and the list of the
-// KMAX smallest per-view costs (BkList).  DESIGN.md section 22 rules 1-2 are the contract of all three.
+// bestk_rules.hpp -- what the best-K kernels (bestk.hip: the plane table or a band around a per-pixel prior; the guide-gated sweep;
+// propagate.hip) have in common.  On the device: a cost's window arithmetic (BkCost) and the list of the KMAX smallest per-view costs
+// (BkList); DESIGN.md section 22 rules 1-2 are the contract of both.  On the host: the one place where (cost, radius, keep) choose an
+// instantiation (with_bestk_shape).  The window elements themselves, zncc_sample and absdiff_sample, are sweep_shared.hpp's.
 #pragma once
 #include "sweep_shared.hpp"
 
 namespace mvs {
 
 constexpr uint32_t BK_NONE = 0xffffffffu;   // the cost of a view that does not count: above every cost, sinks to the end of the list
-
-// band.hip's sample (sweep_fx.hip: sample_global_fx) -> the absolute difference's window element e | ok << 24; a position outside the main
-// frame carries NaN in its affine part (zncc_sample)
-__device__ __forceinline__ uint32_t absdiff_sample(const Affine &A, float bx, float by, float bw, float z, const uint32_t *__restrict__ quads, uint32_t pitch, float hix,
-                                                   float hiy, const uint32_t *__restrict__ lut, uint32_t Im255)
-{
-    const float sx = __builtin_fmaf(z, bx, A.ax), sy = __builtin_fmaf(z, by, A.ay), sw = __builtin_fmaf(z, bw, A.aw);
-    const float r256 = rcp_rn(sw) * 256.0f;
-    const float tx = __builtin_fmaf(sx, r256, ZN_MAGIC + 4.0f), ty = __builtin_fmaf(sy, r256, ZN_MAGIC + 4.0f);
-    const bool ok = sw > 0.0f && tx > ZN_MAGIC + 132.0f && tx < hix && ty > ZN_MAGIC + 132.0f && ty < hiy;  // false for NaN
-    const uint32_t ux = __builtin_bit_cast(uint32_t, tx) & 0x3fffffu, uy = __builtin_bit_cast(uint32_t, ty) & 0x3fffffu;  // t - magic
-    const uint32_t quad = quads[ok ? (uy >> 8) * pitch + (ux >> 8) : 0u];   // in frame: column <= W, row <= H of the (H + 2) x pitch quad image
-    const uint32_t w = lut[(((uy >> 3) & 31u) << 5) | ((ux >> 3) & 31u)];
-    // (the builtin, not inline asm: sweep_fx.hip, sad_u16)
-    const uint32_t cell = __builtin_amdgcn_sad_u16(__builtin_amdgcn_udot4(quad, w, 0u, false), Im255, 1u << 24);
-    return ok ? cell : 0u;
-}
 
 template <int COST>
 struct BkCost;
@@ -82,5 +66,38 @@ struct BkList {
         return cell;
     }
 };
+
+// host: calls f(std::integral_constant<int, COST>, <int, R>, <int, KMAX>) for arguments the entry has checked (cost one of the two, radius
+// RMIN..4 and not 0 with ZNCC, keep 0..8), so that a launcher names its kernel once.  KMAX is the smallest of 0 (MVS_KEEP_ALL), 2, 4, 8
+// that holds `keep`.  ZNCC at radius 0 and the radii below RMIN are never instantiated.
+template <int RMIN, class F>
+inline void with_bestk_shape(int cost, int radius, int keep, F &&f)
+{
+    const auto with_kmax = [&](auto c, auto r) {
+        if constexpr (decltype(r)::value >= RMIN && !(decltype(c)::value == MVS_COST_ZNCC && decltype(r)::value == 0)) {
+            if (keep == MVS_KEEP_ALL)
+                f(c, r, std::integral_constant<int, 0>{});
+            else if (keep <= 2)
+                f(c, r, std::integral_constant<int, 2>{});
+            else if (keep <= 4)
+                f(c, r, std::integral_constant<int, 4>{});
+            else
+                f(c, r, std::integral_constant<int, 8>{});
+        }
+    };
+    const auto with_radius = [&](auto c) {
+        switch (radius) {
+        case 0: with_kmax(c, std::integral_constant<int, 0>{}); break;
+        case 1: with_kmax(c, std::integral_constant<int, 1>{}); break;
+        case 2: with_kmax(c, std::integral_constant<int, 2>{}); break;
+        case 3: with_kmax(c, std::integral_constant<int, 3>{}); break;
+        default: with_kmax(c, std::integral_constant<int, 4>{}); break;
+        }
+    };
+    if (cost == MVS_COST_ZNCC)
+        with_radius(std::integral_constant<int, MVS_COST_ZNCC>{});
+    else
+        with_radius(std::integral_constant<int, MVS_COST_ABSDIFF>{});
+}
 
 }  // namespace mvs

@@ -334,35 +334,6 @@ __global__ __launch_bounds__(256) void propagate_seed(const float *src, float *z
     gy[pix] = g[1];
 }
 
-template <int COST, int R>
-void pass_launch(mvs_ctx *ctx, const SweepParams &p, const PropArgs &a)
-{
-    const dim3 grid((unsigned)div_up(ctx->W, ZN_TW), (unsigned)div_up(ctx->H, ZN_TH));
-    const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
-    if (a.keep == MVS_KEEP_ALL)
-        propagate_pass<COST, R, 0><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, a);
-    else if (a.keep <= 2)
-        propagate_pass<COST, R, 2><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, a);
-    else if (a.keep <= 4)
-        propagate_pass<COST, R, 4><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, a);
-    else
-        propagate_pass<COST, R, 8><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, a);
-}
-
-template <int COST>
-void pass_launch_radius(mvs_ctx *ctx, const SweepParams &p, const PropArgs &a, int radius)
-{
-    switch (radius) {
-    case 0:
-        if constexpr (COST == MVS_COST_ABSDIFF) pass_launch<COST, 0>(ctx, p, a);   // (refused for ZNCC by the caller)
-        break;
-    case 1: pass_launch<COST, 1>(ctx, p, a); break;
-    case 2: pass_launch<COST, 2>(ctx, p, a); break;
-    case 3: pass_launch<COST, 3>(ctx, p, a); break;
-    default: pass_launch<COST, 4>(ctx, p, a); break;
-    }
-}
-
 // one launch of the pass kernel on the recorded cost, radius, keep and view range
 void pass(mvs_ctx *ctx, PropArgs &a)
 {
@@ -381,10 +352,11 @@ void pass(mvs_ctx *ctx, PropArgs &a)
     a.geo = (const PropGeo *)((const char *)maps + prop_tab_offset(P));
     SweepParams p;
     fill_params(ctx, p, ctx->prop_view_first, ctx->prop_view_count, ZN_TH, ZN_PC);
-    if (ctx->prop_cost == MVS_COST_ZNCC)
-        pass_launch_radius<MVS_COST_ZNCC>(ctx, p, a, ctx->prop_radius);
-    else
-        pass_launch_radius<MVS_COST_ABSDIFF>(ctx, p, a, ctx->prop_radius);
+    const dim3 grid((unsigned)div_up(ctx->W, ZN_TW), (unsigned)div_up(ctx->H, ZN_TH));
+    const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
+    with_bestk_shape<0>(ctx->prop_cost, ctx->prop_radius, a.keep, [&](auto c, auto r, auto kmax) {
+        propagate_pass<decltype(c)::value, decltype(r)::value, decltype(kmax)::value><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, a);
+    });
 }
 
 // what init and run refuse alike: the staged state the sampler reads

@@ -118,7 +118,7 @@ __device__ __forceinline__ void store_best(const SweepParams &p, size_t pix, uin
 
 
 // ------------------------------------------------------------------------------------------------------
-// the windowed sweeps' tile (zncc.hip: sweep_fx_zncc, bestk.hip: sweep_fx_bestk) and the ZNCC window element
+// the windowed sweeps' tile (zncc.hip: sweep_fx_zncc, bestk.hip: sweep_fx_bestk) and the two window elements
 // ------------------------------------------------------------------------------------------------------
 constexpr int ZN_TW = 32, ZN_TH = 16;    // pixels per tile
 constexpr int ZN_THREADS = 256;          // two pixels each
@@ -150,6 +150,23 @@ __device__ __forceinline__ uint4 zncc_sample(const Affine &A, float bx, float by
     const uint32_t dot = __builtin_amdgcn_udot4(quad, w, 0u, false);   // <= 65025
     const uint32_t b = (dot + 127u) / 255u;                            // rule 1: the grey level mvs_warp_by_depth returns
     return ok ? make_uint4(a | (b << 16), umul24u(a, b) | (1u << 24), aa, umul24u(b, b)) : make_uint4(0u, 0u, 0u, 0u);
+}
+
+// band.hip's sample (sweep_fx.hip: sample_global_fx) -> the absolute difference's window element e | ok << 24; a position outside the main
+// frame carries NaN in its affine part (zncc_sample)
+__device__ __forceinline__ uint32_t absdiff_sample(const Affine &A, float bx, float by, float bw, float z, const uint32_t *__restrict__ quads, uint32_t pitch, float hix,
+                                                   float hiy, const uint32_t *__restrict__ lut, uint32_t Im255)
+{
+    const float sx = __builtin_fmaf(z, bx, A.ax), sy = __builtin_fmaf(z, by, A.ay), sw = __builtin_fmaf(z, bw, A.aw);
+    const float r256 = rcp_rn(sw) * 256.0f;
+    const float tx = __builtin_fmaf(sx, r256, ZN_MAGIC + 4.0f), ty = __builtin_fmaf(sy, r256, ZN_MAGIC + 4.0f);
+    const bool ok = sw > 0.0f && tx > ZN_MAGIC + 132.0f && tx < hix && ty > ZN_MAGIC + 132.0f && ty < hiy;  // false for NaN
+    const uint32_t ux = __builtin_bit_cast(uint32_t, tx) & 0x3fffffu, uy = __builtin_bit_cast(uint32_t, ty) & 0x3fffffu;  // t - magic
+    const uint32_t quad = quads[ok ? (uy >> 8) * pitch + (ux >> 8) : 0u];   // in frame: column <= W, row <= H of the (H + 2) x pitch quad image
+    const uint32_t w = lut[(((uy >> 3) & 31u) << 5) | ((ux >> 3) & 31u)];
+    // (the builtin, not inline asm: sweep_fx.hip, sad_u16)
+    const uint32_t cell = __builtin_amdgcn_sad_u16(__builtin_amdgcn_udot4(quad, w, 0u, false), Im255, 1u << 24);
+    return ok ? cell : 0u;
 }
 
 // rules 3-5: the window's sums -> the view's contribution to the cell

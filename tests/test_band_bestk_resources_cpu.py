@@ -1,7 +1,7 @@
-"""Resources of the windowed band sweep's kernel (csrc/band_bestk.hip) from the compiler's report for gfx950 with the Makefile's own
-CXXFLAGS: 36 instantiations, as in csrc/bestk.hip -- (five radii of the absolute difference + four of ZNCC) times the four list sizes
-KMAX = 0 (MVS_KEEP_ALL), 2, 4, 8 -- none with scratch or spills.  Registers, occupancy and LDS are printed: the
-per-sample plane costs NS x 2 vector registers over sweep_fx_bestk."""
+"""Resources of the windowed band sweep's kernel (the BAND = true half of csrc/bestk.hip) from the compiler's report for gfx950 with the
+Makefile's own CXXFLAGS: 36 instantiations, as on the plane table -- (five radii of the absolute difference + four of ZNCC) times the
+four list sizes KMAX = 0 (MVS_KEEP_ALL), 2, 4, 8 -- none with scratch or spills.  Registers, occupancy and LDS are
+printed: the per-sample plane costs NS x 2 vector registers over the table's instantiation."""
 import os
 import shutil
 import subprocess
@@ -19,7 +19,7 @@ def resources(tmp_path_factory):
     hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
     assert hipcc, "hipcc is needed to build the library"
     out = str(tmp_path_factory.mktemp("band_bestk") / "band_bestk.o")
-    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", "band_bestk.hip"), "-o", out,
+    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", "bestk.hip"), "-o", out,
                                                       "-Rpass-analysis=kernel-resource-usage"], cwd=PKG, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
     kernels, cur = {}, None
@@ -35,12 +35,13 @@ def resources(tmp_path_factory):
 
 
 def test_every_kernel_of_the_file_is_listed(resources):
-    assert len(INSTANCES) == 36 and len(resources) == len(INSTANCES), sorted(resources)
+    assert len(INSTANCES) == 36 and sum("Lb1EE" in n for n in resources) == len(INSTANCES), sorted(resources)
+    assert not os.path.exists(os.path.join(PKG, "csrc", "band_bestk.hip"))   # one tile kernel: no second copy of the body
 
 
 @pytest.mark.parametrize("cost,r,kmax", INSTANCES)
 def test_no_scratch_and_no_spills(resources, cost, r, kmax):
-    tag = "19sweep_fx_band_bestkILi%dELi%dELi%dEE" % (cost, r, kmax)
+    tag = "14sweep_fx_bestkILi%dELi%dELi%dELb1EE" % (cost, r, kmax)
     names = [n for n in resources if tag in n]
     assert len(names) == 1, sorted(resources)
     k = resources[names[0]]

@@ -1,6 +1,7 @@
-"""Resources of the occlusion-robust sweep's kernel (csrc/bestk.hip) from the compiler's report for gfx950 with the Makefile's own
-CXXFLAGS: no scratch and no spills in any instantiation: (five radii of the absolute difference + four of ZNCC)
-times the four list sizes KMAX = 0 (MVS_KEEP_ALL), 2, 4, 8.  `keep` and the two outputs are kernel arguments."""
+"""Resources of the windowed sweeps' tile kernel (csrc/bestk.hip) from the compiler's report for gfx950 with the Makefile's own CXXFLAGS:
+no scratch and no spills in any instantiation: (five radii of the absolute difference + four of ZNCC) times the
+four list sizes KMAX = 0 (MVS_KEEP_ALL), 2, 4, 8, here on the plane table (BAND = false); tests/test_band_bestk_resources_cpu.py has
+the other half of the file's 72 kernels.  `keep` and the two outputs are kernel arguments."""
 import os
 import shutil
 import subprocess
@@ -34,12 +35,12 @@ def resources(tmp_path_factory):
 
 
 def test_every_kernel_of_the_file_is_listed(resources):
-    assert len(INSTANCES) == 36 and len(resources) == len(INSTANCES), sorted(resources)
+    assert len(INSTANCES) == 36 and len(resources) == 2 * len(INSTANCES), sorted(resources)   # x BAND
 
 
 @pytest.mark.parametrize("cost,r,kmax", INSTANCES)
 def test_no_scratch_and_no_spills(resources, cost, r, kmax):
-    tag = "14sweep_fx_bestkILi%dELi%dELi%dEE" % (cost, r, kmax)
+    tag = "14sweep_fx_bestkILi%dELi%dELi%dELb0EE" % (cost, r, kmax)
     names = [n for n in resources if tag in n]
     assert len(names) == 1, sorted(resources)
     k = resources[names[0]]

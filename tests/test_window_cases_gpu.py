@@ -1,6 +1,6 @@
 """The windowed sweeps, the band sweeps and the propagation on the crafted cases of tests/window_cameras.py: every kernel that carries a copy
-of the fixed sampler -- zncc.hip, bestk.hip, bestk_gated.hip, band_bestk.hip and propagate.hip through zncc_sample / absdiff_sample,
-band.hip through band_sample -- equals the mirrors built on tests/sweep_mirror.py's samples on volume, depth, cost and index (the band
+of the fixed sampler -- zncc.hip, bestk.hip (the table and band sweeps), bestk_gated.hip and propagate.hip through zncc_sample /
+absdiff_sample, band.hip through absdiff_sample -- equals the mirrors built on tests/sweep_mirror.py's samples on volume, depth, cost and index (the band
 sweeps also on the resolved map and the report, the propagation on z, gx, gy, cells, cost map and report), by exact equality: no cell
 budget.  Between two runs a run over zero views empties volume and maps, so no run can pass on what its predecessor left.  One context
 per frame size serves every case of that size."""
@@ -145,7 +145,7 @@ def test_gated_equals_the_mirror(contexts, name, tau):
                     "%s, %s r = %d keep = %d, tau = %d" % (name, wc.COST_NAMES[cost], r, keep, tau))
 
 
-# ---- band.hip, band_bestk.hip --------------------------------------------------------------------------------------------------------
+# ---- band.hip, the band entry of bestk.hip -------------------------------------------------------------------------------------------
 def _band_maps(ctx, c, vol, what):
     """the maps hold offsets; then the resolved map and the report"""
     want = wc.maps(vol, c.z())

@@ -1,7 +1,7 @@
 """Crafted cameras for the windowed sweeps and the propagation ("Crafted cameras for the windowed kernels"): the cases of
 tests/sweep_cameras.py that put a sample ON the frame test's bounds, on a rounding tie or on s.w == 0, and cases of their own at the
-edges of the window arithmetic.  Every kernel that carries a copy of the fixed sampler (zncc.hip, bestk.hip, bestk_gated.hip,
-band_bestk.hip, propagate.hip through zncc_sample / absdiff_sample; band.hip through band_sample) runs on them.
+edges of the window arithmetic.  Every kernel that carries a copy of the fixed sampler (zncc.hip, bestk.hip for the table and band
+sweeps, bestk_gated.hip, propagate.hip through zncc_sample / absdiff_sample; band.hip through absdiff_sample) runs on them.
 
 The samples come from tests/sweep_mirror.py alone (sample_fixed: the contract of section 2b restated without the oracle), on the plane
 table or, for the band sweeps, on the per-pixel plane map prior + offset.  On top of them stand the PURE functions of the windowed

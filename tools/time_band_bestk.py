@@ -1,4 +1,4 @@
-"""Time the band sweep with windowed costs (csrc/band_bestk.hip) beside the sweeps it joins, in one process, after
+"""Time the band sweep with windowed costs (csrc/bestk.hip) beside the sweeps it joins, in one process, after
 warm-up.
 
 The two cases of tools/time_band.py: 640 x 480 x 32 planes x 4 views on the cameras of the bundled zatisi.yaml (noise frames) and
