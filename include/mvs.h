@@ -166,7 +166,17 @@ int mvs_warp_by_depth(mvs_ctx *ctx, const float main_cam[16], const float *depth
  *   MVS_SAMPLER_EXACT_F32: bilinear interpolation in f32 with one rounding per operation, result rounded to u8 like the RGB8
  *     read-back; a packed cell is count << 16 | sum |u8 - I_main| (at most 257 views).
  * Both are restated bit for bit by the CPU oracle; they select the same plane except where two planes' costs are within the
- * quantisation step (measured: DESIGN.md).  Changing the sampler invalidates the region plan, not the uploaded inputs. */
+ * quantisation step (measured: DESIGN.md).  Changing the sampler invalidates the region plan, not the uploaded inputs.
+ * The RESULTS stay in the layout they were written in: the context records the sampler under which the library last wrote the packed
+ * volume (any sweep with MVS_SWEEP_VOLUME) and the windowed volume Wv (mvs_sweep_window); for a caller's volume the layout is unknown
+ * until a sweep writes it (mvs_sweep_use_volume).  A reader that would decode cells of a known layout under the other sampler --
+ * mvs_sweep_argmin, _refine_depth, _aggregate, _clean (through mvs_sweep_set_volume_source's volume), mvs_sweep_window and
+ * mvs_sweep_fetch with a packed_volume_dhw -- returns MVS_ESTATE, names both samplers and changes nothing; switching back makes the cells
+ * readable again, and so does the next sweep.  A row band (mvs_sweep_run_rows) or plane group (mvs_sweep_run_planes) written under the
+ * other sampler than the rest of the volume leaves cells of both layouts: the readers then return MVS_ESTATE under either sampler until
+ * one sweep has written all rows and planes.  mvs_sweep_argmin_partial and mvs_sweep_combine_partials take the caller's pointers and
+ * decode them as the current sampler's.  The depth / cost / index maps, S, the clean report and the band depth hold no cells and stay
+ * readable. */
 #define MVS_SAMPLER_FIXED 0
 #define MVS_SAMPLER_EXACT_F32 1
 int mvs_sweep_set_sampler(mvs_ctx *ctx, int sampler);
@@ -347,7 +357,7 @@ int mvs_sweep_volume_source(const mvs_ctx *ctx);
  * Errors: MVS_EINVAL for a NULL ctx, prior or array, a view range outside 0..V, flags that select neither output, unknown flag bits
  * (MVS_SWEEP_FORCE_GENERIC and MVS_SWEEP_NO_RECT are unknown here); MVS_ESTATE without main view, views or planes, for a plane table not
  * inside (-1, 1), for the exact sampler; MVS_ESTATE from resolve, fetch and report before a band run, after an ordinary mvs_sweep_run*
- * since, without a depth selection over the current plane count, when the plane count has changed since the band run, and from fetch and
+ * or a new prior (mvs_pyramid_prior into this context's prior buffer) since, without a depth selection over the current plane count, when the plane count has changed since the band run, and from fetch and
  * report before the band run's resolve; MVS_ENOMEM.  After an error nothing is written and the context stays usable. */
 int mvs_sweep_run_band(mvs_ctx *ctx, int view_first, int view_count, const void *prior_dev, unsigned flags);
 int mvs_sweep_band_resolve(mvs_ctx *ctx);
@@ -495,6 +505,9 @@ int mvs_sweep_run_band_bestk(mvs_ctx *ctx, int view_first, int view_count, const
  *      context's depth map (mvs_sweep_depth_device(coarse), after a refined sweep); mvs_sweep_band_depth_device(coarse) when the coarse
  *      level was itself a band level -- into the fine context's own prior buffer, the one mvs_sweep_band_prior_device(fine) returns
  *      (allocated if need be), so mvs_sweep_run_band(fine, v0, n, mvs_sweep_band_prior_device(fine), flags) runs without a copy.
+ *      That buffer is also the prior of fine's LAST band run, which mvs_sweep_band_resolve adds the offsets to: the call therefore ENDS
+ *      that band run, resolved or not -- mvs_sweep_band_resolve, _fetch and _report return MVS_ESTATE until the next band run (fetch a
+ *      resolved map before asking for the next prior).  The maps, the volume and the selection of `fine` stay as they are.
  * Ordering between the two contexts' streams is the library's job: a kernel that reads one context's buffers and writes the other's
  * runs on the consumer's stream behind an event recorded on the producer's stream, and the producer's stream then waits for an event
  * recorded behind that kernel, so the producer's next work cannot overwrite what is still being read.  The events are created once per

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void band_resolve(const float *__restrict__ pr
 // the planes the band run had
 int band_state(mvs_ctx *ctx, const char *who)
 {
-    if (!ctx->band_planes) return fail(ctx, MVS_ESTATE, "%s: no band run yet, or an ordinary sweep since (mvs_sweep_run_band first)", who);
+    if (!ctx->band_planes) return fail(ctx, MVS_ESTATE, "%s: no band run yet, or an ordinary sweep or a new prior (mvs_pyramid_prior) since (mvs_sweep_run_band first)", who);
     if (!ctx->have_planes || ctx->D != ctx->band_planes)
         return fail(ctx, MVS_ESTATE, "%s: the band run had %d planes, the context now has %d (run the band again)", who, ctx->band_planes, ctx->D);
     if (!selection_current(ctx) || !ctx->index.ptr)
@@ -163,6 +163,7 @@ int mvs_sweep_run_band(mvs_ctx *ctx, int view_first, int view_count, const void 
     MVS_HIP(ctx, hipGetLastError());
     ctx->band_planes = ctx->D;
     ctx->band_resolved = false;
+    if (vol) note_volume_written(ctx);
     fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }

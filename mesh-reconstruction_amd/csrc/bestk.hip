@@ -236,6 +236,7 @@ int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, 
     }
     MVS_HIP(ctx, hipGetLastError());
     note_ordinary_sweep(ctx);
+    if (vol) note_volume_written(ctx);
     fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }
@@ -268,6 +269,7 @@ int mvs_sweep_run_band_bestk(mvs_ctx *ctx, int view_first, int view_count, const
     MVS_HIP(ctx, hipGetLastError());
     ctx->band_planes = ctx->D;   // the band state, exactly as mvs_sweep_run_band leaves it
     ctx->band_resolved = false;
+    if (vol) note_volume_written(ctx);
     fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }

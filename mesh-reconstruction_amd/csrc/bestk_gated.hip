@@ -210,6 +210,7 @@ int mvs_sweep_run_bestk_gated(mvs_ctx *ctx, int view_first, int view_count, int 
     }
     MVS_HIP(ctx, hipGetLastError());
     note_ordinary_sweep(ctx);
+    if (g.vol) note_volume_written(ctx);
     g.fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }

@@ -70,6 +70,12 @@ struct mvs_ctx {
     bool have_main = false, have_views = false, have_planes = false;
     bool plan_valid = false;         // region plan matches current (views, planes)
     int sampler = MVS_SAMPLER_FIXED;  // arithmetic contract of the sweep's texture fetch (mvs_sweep_set_sampler)
+    // the sampler whose cell layout the library last wrote the current packed volume / Wv in (-1: unknown -- nothing written yet, or a
+    // caller's volume the library has not written since mvs_sweep_use_volume); own_cells_sampler keeps the own volume's while a caller's
+    // is in use.  A reader under another sampler would decode the cells wrongly and refuses (mvs::cells_readable)
+    // CELLS_MIXED: a row band or plane group was written under another sampler than the rest: no reader until a sweep writes all of it
+    static constexpr int CELLS_MIXED = -2;
+    int vol_cells_sampler = -1, own_cells_sampler = -1, win_cells_sampler = -1;
     mvs::DevBuf side_quads;          // fixed sampler: quad image of every padded side view (4 bytes per texel), built by mvs_sweep_set_views
     mvs::DevBuf side_quads16;        // exact sampler: f16 quad image (8 bytes per texel), built on demand by ensure_quads16
     bool quads16_valid = false;
@@ -327,6 +333,13 @@ void note_rows_selected(mvs_ctx *ctx, int r0, int r1);
 inline void note_no_selection(mvs_ctx *ctx) { ctx->sel_planes = ctx->sel_band_planes = 0; }
 // an ordinary sweep has run: the volume and the maps stop being a band run's (mvs_sweep_band_resolve refuses from here on)
 inline void note_ordinary_sweep(mvs_ctx *ctx) { ctx->band_planes = 0; }
+// the prior buffer was rewritten behind a band run (mvs_pyramid_prior): the offsets in the depth map were measured from the old prior
+inline void note_new_prior(mvs_ctx *ctx) { ctx->band_planes = 0; }
+// a sweep has written cells into the current packed volume: they have the layout of the current sampler
+inline void note_volume_written(mvs_ctx *ctx) { ctx->vol_cells_sampler = ctx->sampler; }
+// select.hip: MVS_ESTATE when cells written under `cells_sampler` (-1: unknown, readable) would be decoded in the current sampler's layout,
+// or when they are a mixture of both layouts (CELLS_MIXED)
+int cells_readable(mvs_ctx *ctx, const char *who, const char *what, int cells_sampler);
 
 // the sweep's input setters with the final synchronisation optional (context.hip; mvs_sweep queues all of them and waits once)
 int sweep_set_main_impl(mvs_ctx *ctx, const float main_cam[16], const uint8_t *main_hw, bool sync, bool device = false);

@@ -227,6 +227,7 @@ int mvs_pyramid_prior(mvs_ctx *fine, mvs_ctx *coarse, const void *coarse_depth_d
         pyramid_prior<<<dim3((unsigned)div_up(fine->W, 64), (unsigned)div_up(fine->H, 4)), 256, 0, fine->stream>>>(zc, gc, gf, (float *)fine->band_prior.ptr, fine->W, fine->H, tau);
     }
     MVS_HIP(fine, hipGetLastError());
+    note_new_prior(fine);
     MVS_HIP(fine, hipEventRecord(fine->pyr_events[1], fine->stream));
     MVS_HIP(coarse, hipStreamWaitEvent(coarse->stream, fine->pyr_events[1], 0));
     return MVS_OK;

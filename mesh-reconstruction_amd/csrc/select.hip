@@ -149,18 +149,31 @@ int unpack_volume_launch(mvs_ctx *ctx, const uint32_t *vol, float *out, size_t n
     return MVS_OK;
 }
 
+int cells_readable(mvs_ctx *ctx, const char *who, const char *what, int cells_sampler)
+{
+    static const char *const names[2] = {"MVS_SAMPLER_FIXED", "MVS_SAMPLER_EXACT_F32"};
+    if (cells_sampler == mvs_ctx::CELLS_MIXED)
+        return fail(ctx, MVS_ESTATE, "%s: %s holds cells of both samplers' layouts (a row band or plane group swept after a sampler switch): sweep all of it first", who,
+                    what);
+    if (cells_sampler < 0 || cells_sampler == ctx->sampler) return MVS_OK;
+    return fail(ctx, MVS_ESTATE, "%s: %s was written under %s and the context's sampler now is %s, whose cells have another layout (sweep again, or switch back)", who,
+                what, names[cells_sampler == MVS_SAMPLER_FIXED ? 0 : 1], names[ctx->sampler == MVS_SAMPLER_FIXED ? 0 : 1]);
+}
+
 int reader_volume(mvs_ctx *ctx, const char *who, const uint32_t *&vol, size_t &bytes)
 {
+    vol = nullptr;
+    bytes = 0;
     if (ctx->volume_source != MVS_VOLUME_WINDOWED) {
+        if (int rc = cells_readable(ctx, who, "the packed volume", ctx->vol_cells_sampler)) return rc;
         vol = ctx->volume;
         bytes = ctx->volume_bytes;
         return MVS_OK;
     }
-    vol = nullptr;
-    bytes = 0;
     if (!ctx->have_planes || !ctx->win_planes || ctx->win_planes != ctx->D)
         return fail(ctx, MVS_ESTATE, "%s: the volume source is MVS_VOLUME_WINDOWED and there is no windowed volume of the current %d planes (mvs_sweep_window first)", who,
                     ctx->D);
+    if (int rc = cells_readable(ctx, who, "the windowed volume", ctx->win_cells_sampler)) return rc;
     vol = (const uint32_t *)ctx->win_vol.ptr;
     bytes = (size_t)ctx->win_planes * ctx->W * ctx->H * sizeof(uint32_t);
     return MVS_OK;

@@ -278,6 +278,7 @@ int mvs_sweep_window(mvs_ctx *ctx, int radius, int tau, const void *guide_dev, u
     if (!ctx->have_planes || D < 1) return fail(ctx, MVS_ESTATE, "mvs_sweep_window: no planes (mvs_sweep_set_planes first)");
     if (!ctx->volume || ctx->volume_bytes < N * sizeof(uint32_t))
         return fail(ctx, MVS_ESTATE, "mvs_sweep_window: no packed volume of %d x %d x %d cells (mvs_sweep_run with MVS_SWEEP_VOLUME)", D, H, W);
+    if (int rc = cells_readable(ctx, "mvs_sweep_window", "the packed volume", ctx->vol_cells_sampler)) return rc;
     const bool gated = radius > 0 && tau < 255;
     const uint8_t *guide = guide_dev ? (const uint8_t *)guide_dev : (ctx->have_main ? main_image_ptr(ctx) : nullptr);
     if (gated && !guide) return fail(ctx, MVS_ESTATE, "mvs_sweep_window: tau %d needs a guide image: pass one, or stage a main image (mvs_sweep_set_main)", tau);
@@ -324,6 +325,7 @@ int mvs_sweep_window(mvs_ctx *ctx, int radius, int tau, const void *guide_dev, u
     }
     MVS_HIP(ctx, hipGetLastError());
     ctx->win_planes = D;
+    ctx->win_cells_sampler = ctx->sampler;
     if (select) note_full_selection(ctx);
     return MVS_OK;
 }

@@ -167,6 +167,7 @@ int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius,
     }
     MVS_HIP(ctx, hipGetLastError());
     note_ordinary_sweep(ctx);
+    if (vol) note_volume_written(ctx);
     fused ? note_full_selection(ctx) : note_no_selection(ctx);
     return MVS_OK;
 }

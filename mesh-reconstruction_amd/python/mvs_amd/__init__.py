@@ -1605,7 +1605,8 @@ class Context:
     def pyramid_prior(self, coarse, depth_ptr=None, tau=255):
         """mvs_pyramid_prior: the coarse level's depth map (depth_ptr: device address of (H/2)*(W/2) f32; None: coarse's own depth map)
         upsampled into this context's prior buffer, sweep_band_pointers()[1], which is returned; tau < 255 keeps to the taps whose guide
-        pixel is within tau grey levels of this pixel's (the staged main images are the guides)"""
+        pixel is within tau grey levels of this pixel's (the staged main images are the guides).  A new prior ends this context's band run:
+        sweep_band_resolve / _report refuse until the next one"""
         self._check(self.lib.mvs_pyramid_prior(self.h, coarse.h, C.c_void_p(int(depth_ptr)) if depth_ptr else None, int(tau)))
         return self.lib.mvs_sweep_band_prior_device(self.h)
 
