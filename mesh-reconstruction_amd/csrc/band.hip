@@ -19,8 +19,6 @@
 
 namespace mvs {
 
-int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the 32 x 32 weight table on the device
-
 namespace {
 
 constexpr int BAND_TW = 32, BAND_TH = 8;   // pixels per tile: 256 threads
@@ -138,34 +136,11 @@ int mvs_sweep_run_band(mvs_ctx *ctx, int view_first, int view_count, const void 
 {
     if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_sweep_run_band: null context");
     if (!prior_dev) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_band: prior_dev is null");
-    bool vol, fused;
-    int rc;
-    if ((rc = fx_sweep_preconditions(ctx, "mvs_sweep_run_band", view_first, view_count, flags, vol, fused))) return rc;
-    for (int d = 0; d < ctx->D; d++)
-        if (!(ctx->z_host[d] > -1.0f && ctx->z_host[d] < 1.0f))
-            return fail(ctx, MVS_ESTATE, "mvs_sweep_run_band: the plane table holds the band's offsets and must lie inside (-1, 1): offset %d is %g", d, ctx->z_host[d]);
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t P = (size_t)ctx->W * ctx->H;
-    if ((rc = sweep_outputs(ctx, vol, "mvs_sweep_run_band"))) return rc;
-    if ((rc = ensure(ctx, ctx->band_prior, P * sizeof(float)))) return rc;
-    if ((rc = ensure_fx_lut(ctx))) return rc;
-    // the context's own copy: the caller's map may be the depth map this run overwrites (stream order puts the copy first)
-    if (prior_dev != ctx->band_prior.ptr) MVS_HIP(ctx, hipMemcpyAsync(ctx->band_prior.ptr, prior_dev, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    SweepParams p;
-    fill_params(ctx, p, view_first, view_count, BAND_TH, BAND_PC);
-    const dim3 grid((unsigned)div_up(ctx->W, BAND_TW), (unsigned)div_up(ctx->H, BAND_TH));
-    const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
-    const float *prior = (const float *)ctx->band_prior.ptr;
-    {
-        ProfileScope ps(ctx, MVS_K_SWEEP);
-        with_outputs(vol, fused, [&](auto v, auto f) { sweep_fx_band<decltype(v)::value, decltype(f)::value><<<grid, 256, 0, ctx->stream>>>(p, lut, prior); });
-    }
-    MVS_HIP(ctx, hipGetLastError());
-    ctx->band_planes = ctx->D;
-    ctx->band_resolved = false;
-    if (vol) note_volume_written(ctx);
-    fused ? note_full_selection(ctx) : note_no_selection(ctx);
-    return MVS_OK;
+    return fx_sweep_run(ctx, {"mvs_sweep_run_band", view_first, view_count, flags, prior_dev, BAND_TH, BAND_PC},
+                        [&](const SweepParams &p, const uint32_t *lut, const float *prior, bool vol, bool fused) {
+                            const dim3 grid((unsigned)div_up(ctx->W, BAND_TW), (unsigned)div_up(ctx->H, BAND_TH));
+                            with_outputs(vol, fused, [&](auto v, auto f) { sweep_fx_band<decltype(v)::value, decltype(f)::value><<<grid, 256, 0, ctx->stream>>>(p, lut, prior); });
+                        });
 }
 
 int mvs_sweep_band_resolve(mvs_ctx *ctx)
@@ -184,7 +159,7 @@ int mvs_sweep_band_resolve(mvs_ctx *ctx)
                                                                          (float *)ctx->band_depth.ptr, (int *)ctx->band_counters.ptr, P, ctx->D);
     }
     MVS_HIP(ctx, hipGetLastError());
-    ctx->band_resolved = true;
+    note_band_resolved(ctx);
     return MVS_OK;
 }
 

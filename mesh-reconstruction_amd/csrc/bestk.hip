@@ -40,11 +40,9 @@
 //     nothing measurable).
 //   The body stays inside the one __global__ template: a thin kernel per sweep around a __forceinline__ body cost 6 vector registers and
 //     a wave per SIMD in most instantiations.
-#include "bestk_rules.hpp"   // BkCost, BkList, with_bestk_shape
+#include "bestk_rules.hpp"   // BkCost, BkList, with_bestk_shape, bestk_arguments
 
 namespace mvs {
-
-int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the 32 x 32 weight table on the device
 
 namespace {
 
@@ -187,16 +185,6 @@ __global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk(SweepParams p, cons
     }
 }
 
-// what the two entries refuse alike
-int bestk_arguments(mvs_ctx *ctx, const char *who, int cost, int radius, int keep)
-{
-    if (cost != MVS_COST_ABSDIFF && cost != MVS_COST_ZNCC) return fail(ctx, MVS_EINVAL, "%s: unknown cost %d", who, cost);
-    const int rmin = cost == MVS_COST_ZNCC ? 1 : 0;
-    if (radius < rmin || radius > 4) return fail(ctx, MVS_EINVAL, "%s: radius %d outside %d..4", who, radius, rmin);
-    if (keep < 0 || keep > 8) return fail(ctx, MVS_EINVAL, "%s: keep %d outside 1..8 and not MVS_KEEP_ALL", who, keep);
-    return MVS_OK;
-}
-
 // the launch for checked (cost, radius, keep); `prior` non-null: the band's planes prior + delta
 void bestk_tile_launch(mvs_ctx *ctx, const SweepParams &p, const float *prior, int cost, int radius, int keep, bool vol, bool fused)
 {
@@ -221,24 +209,10 @@ int mvs_sweep_run_bestk(mvs_ctx *ctx, int view_first, int view_count, int cost, 
 {
     static const char who[] = "mvs_sweep_run_bestk";
     if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
-    bool vol, fused;
-    int rc;
-    if ((rc = bestk_arguments(ctx, who, cost, radius, keep))) return rc;
-    if ((rc = fx_sweep_preconditions(ctx, who, view_first, view_count, flags, vol, fused))) return rc;
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = sweep_outputs(ctx, vol, who))) return rc;
-    if ((rc = ensure_fx_lut(ctx))) return rc;
-    SweepParams p;
-    fill_params(ctx, p, view_first, view_count, ZN_TH, ZN_PC);
-    {
-        ProfileScope ps(ctx, MVS_K_SWEEP);
-        bestk_tile_launch(ctx, p, nullptr, cost, radius, keep, vol, fused);
-    }
-    MVS_HIP(ctx, hipGetLastError());
-    note_ordinary_sweep(ctx);
-    if (vol) note_volume_written(ctx);
-    fused ? note_full_selection(ctx) : note_no_selection(ctx);
-    return MVS_OK;
+    if (int rc = bestk_arguments(ctx, who, cost, radius, keep)) return rc;
+    return fx_sweep_run(ctx, {who, view_first, view_count, flags, nullptr, ZN_TH, ZN_PC}, [&](const SweepParams &p, const uint32_t *, const float *prior, bool vol, bool fused) {
+        bestk_tile_launch(ctx, p, prior, cost, radius, keep, vol, fused);
+    });
 }
 
 int mvs_sweep_run_band_bestk(mvs_ctx *ctx, int view_first, int view_count, const void *prior_dev, int cost, int radius, int keep, unsigned flags)
@@ -246,30 +220,8 @@ int mvs_sweep_run_band_bestk(mvs_ctx *ctx, int view_first, int view_count, const
     static const char who[] = "mvs_sweep_run_band_bestk";
     if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
     if (!prior_dev) return fail(ctx, MVS_EINVAL, "%s: prior_dev is null", who);
-    bool vol, fused;
-    int rc;
-    if ((rc = bestk_arguments(ctx, who, cost, radius, keep))) return rc;
-    if ((rc = fx_sweep_preconditions(ctx, who, view_first, view_count, flags, vol, fused))) return rc;
-    for (int d = 0; d < ctx->D; d++)
-        if (!(ctx->z_host[d] > -1.0f && ctx->z_host[d] < 1.0f))
-            return fail(ctx, MVS_ESTATE, "%s: the plane table holds the band's offsets and must lie inside (-1, 1): offset %d is %g", who, d, ctx->z_host[d]);
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t P = (size_t)ctx->W * ctx->H;
-    if ((rc = sweep_outputs(ctx, vol, who))) return rc;
-    if ((rc = ensure(ctx, ctx->band_prior, P * sizeof(float)))) return rc;
-    if ((rc = ensure_fx_lut(ctx))) return rc;
-    // the context's own copy: the caller's map may be the depth map this run overwrites (stream order puts the copy first)
-    if (prior_dev != ctx->band_prior.ptr) MVS_HIP(ctx, hipMemcpyAsync(ctx->band_prior.ptr, prior_dev, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    SweepParams p;
-    fill_params(ctx, p, view_first, view_count, ZN_TH, ZN_PC);
-    {
-        ProfileScope ps(ctx, MVS_K_SWEEP);
-        bestk_tile_launch(ctx, p, (const float *)ctx->band_prior.ptr, cost, radius, keep, vol, fused);
-    }
-    MVS_HIP(ctx, hipGetLastError());
-    ctx->band_planes = ctx->D;   // the band state, exactly as mvs_sweep_run_band leaves it
-    ctx->band_resolved = false;
-    if (vol) note_volume_written(ctx);
-    fused ? note_full_selection(ctx) : note_no_selection(ctx);
-    return MVS_OK;
+    if (int rc = bestk_arguments(ctx, who, cost, radius, keep)) return rc;
+    return fx_sweep_run(ctx, {who, view_first, view_count, flags, prior_dev, ZN_TH, ZN_PC}, [&](const SweepParams &p, const uint32_t *, const float *prior, bool vol, bool fused) {
+        bestk_tile_launch(ctx, p, prior, cost, radius, keep, vol, fused);
+    });
 }

@@ -20,8 +20,6 @@
 
 namespace mvs {
 
-int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the 32 x 32 weight table on the device
-
 namespace {
 
 // the element where m is all ones, exact zeros where m is 0
@@ -169,12 +167,6 @@ __global__ __launch_bounds__(ZN_THREADS) void sweep_fx_bestk_gated(SweepParams p
     }
 }
 
-struct GateArgs {
-    const uint8_t *guide;
-    int tau, keep;
-    bool vol, fused;
-};
-
 }  // namespace
 
 }  // namespace mvs
@@ -189,28 +181,11 @@ int mvs_sweep_run_bestk_gated(mvs_ctx *ctx, int view_first, int view_count, int 
     if (radius < 1 || radius > 4) return fail(ctx, MVS_EINVAL, "%s: radius %d outside 1..4 (radius 0 has no window to gate)", who, radius);
     if (keep < 0 || keep > 8) return fail(ctx, MVS_EINVAL, "%s: keep %d outside 1..8 and not MVS_KEEP_ALL", who, keep);
     if (tau < 0 || tau > 255) return fail(ctx, MVS_EINVAL, "%s: tau %d outside 0..255", who, tau);
-    GateArgs g;
-    int rc;
-    if ((rc = fx_sweep_preconditions(ctx, who, view_first, view_count, flags, g.vol, g.fused))) return rc;
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = sweep_outputs(ctx, g.vol, who))) return rc;
-    if ((rc = ensure_fx_lut(ctx))) return rc;
-    SweepParams p;
-    fill_params(ctx, p, view_first, view_count, ZN_TH, ZN_PC);
-    g.guide = guide_dev ? (const uint8_t *)guide_dev : p.main_img;   // (the preconditions hold that a main image is staged)
-    g.tau = tau;
-    g.keep = keep;
-    {
-        ProfileScope ps(ctx, MVS_K_SWEEP);
+    return fx_sweep_run(ctx, {who, view_first, view_count, flags, nullptr, ZN_TH, ZN_PC}, [&](const SweepParams &p, const uint32_t *lut, const float *, bool vol, bool fused) {
         const dim3 grid((unsigned)div_up(ctx->W, ZN_TW), (unsigned)div_up(ctx->H, ZN_TH));
-        const uint32_t *lut = (const uint32_t *)ctx->fx_lut.ptr;
+        const uint8_t *guide = guide_dev ? (const uint8_t *)guide_dev : p.main_img;   // (the preconditions hold that a main image is staged)
         with_bestk_shape<1>(cost, radius, keep, [&](auto c, auto r, auto kmax) {
-            sweep_fx_bestk_gated<decltype(c)::value, decltype(r)::value, decltype(kmax)::value><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, g.guide, g.tau, g.keep, g.vol, g.fused);
+            sweep_fx_bestk_gated<decltype(c)::value, decltype(r)::value, decltype(kmax)::value><<<grid, ZN_THREADS, 0, ctx->stream>>>(p, lut, guide, tau, keep, vol, fused);
         });
-    }
-    MVS_HIP(ctx, hipGetLastError());
-    note_ordinary_sweep(ctx);
-    if (g.vol) note_volume_written(ctx);
-    g.fused ? note_full_selection(ctx) : note_no_selection(ctx);
-    return MVS_OK;
+    });
 }

@@ -67,6 +67,16 @@ struct BkList {
     }
 };
 
+// host: what the best-K entries (`who`: the two sweeps of bestk.hip, mvs_propagate_init) refuse alike
+inline int bestk_arguments(mvs_ctx *ctx, const char *who, int cost, int radius, int keep)
+{
+    if (cost != MVS_COST_ABSDIFF && cost != MVS_COST_ZNCC) return fail(ctx, MVS_EINVAL, "%s: unknown cost %d", who, cost);
+    const int rmin = cost == MVS_COST_ZNCC ? 1 : 0;
+    if (radius < rmin || radius > 4) return fail(ctx, MVS_EINVAL, "%s: radius %d outside %d..4", who, radius, rmin);
+    if (keep < 0 || keep > 8) return fail(ctx, MVS_EINVAL, "%s: keep %d outside 1..8 and not MVS_KEEP_ALL", who, keep);
+    return MVS_OK;
+}
+
 // host: calls f(std::integral_constant<int, COST>, <int, R>, <int, KMAX>) for arguments the entry has checked (cost one of the two, radius
 // RMIN..4 and not 0 with ZNCC, keep 0..8), so that a launcher names its kernel once.  KMAX is the smallest of 0 (MVS_KEEP_ALL), 2, 4, 8
 // that holds `keep`.  ZNCC at radius 0 and the radii below RMIN are never instantiated.

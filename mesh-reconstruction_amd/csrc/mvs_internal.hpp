@@ -320,7 +320,8 @@ inline size_t volume_need(const mvs_ctx *ctx) { return (size_t)ctx->W * ctx->H *
 inline bool volume_holds_planes(const mvs_ctx *ctx, const uint32_t *vol, size_t bytes) { return ctx->have_planes && vol && bytes >= volume_need(ctx); }
 inline bool selection_current(const mvs_ctx *ctx) { return ctx->sel_planes == ctx->D; }
 
-// The selection state (sel_planes, sel_band_*, band_planes) changes through these transitions only.
+// The state DESIGN.md section 30 tabulates (sel_planes, sel_band_*, band_planes, band_resolved, the three *_cells_sampler, win_planes;
+// section 13 for the selection) changes through these transitions only; tests/test_shadow_cpu.py holds that over the sources.
 // A writer of every row of ctx->index has been launched over the current planes:
 inline void note_full_selection(mvs_ctx *ctx)
 {
@@ -337,6 +338,49 @@ inline void note_ordinary_sweep(mvs_ctx *ctx) { ctx->band_planes = 0; }
 inline void note_new_prior(mvs_ctx *ctx) { ctx->band_planes = 0; }
 // a sweep has written cells into the current packed volume: they have the layout of the current sampler
 inline void note_volume_written(mvs_ctx *ctx) { ctx->vol_cells_sampler = ctx->sampler; }
+// a band run has been launched: the volume and the maps are its, and no resolve of it has run yet
+inline void note_band_run(mvs_ctx *ctx)
+{
+    ctx->band_planes = ctx->D;
+    ctx->band_resolved = false;
+}
+// mvs_sweep_band_resolve has been launched: band_depth belongs to the last band run
+inline void note_band_resolved(mvs_ctx *ctx) { ctx->band_resolved = true; }
+// the epilogue of a fixed-sampler sweep entry (sweep_shared.hpp: fx_sweep_run) that wrote all rows and planes: a band run or an ordinary
+// one, with or without the volume, with or without a depth selection
+inline void note_fx_sweep(mvs_ctx *ctx, bool band, bool vol, bool fused)
+{
+    band ? note_band_run(ctx) : note_ordinary_sweep(ctx);
+    if (vol) note_volume_written(ctx);
+    fused ? note_full_selection(ctx) : note_no_selection(ctx);
+}
+// mvs_sweep_run has written the whole volume or a row band / plane group of it: a part written under another sampler than the rest was
+// written with leaves cells of both layouts until a sweep writes all of it
+inline void note_volume_part_written(mvs_ctx *ctx, bool whole)
+{
+    if (whole || ctx->vol_cells_sampler == -1 || ctx->vol_cells_sampler == ctx->sampler)
+        note_volume_written(ctx);
+    else
+        ctx->vol_cells_sampler = mvs_ctx::CELLS_MIXED;
+}
+// mvs_sweep_window has been launched over the current planes / has replaced Wv's buffer and not yet launched
+inline void note_window_written(mvs_ctx *ctx)
+{
+    ctx->win_planes = ctx->D;
+    ctx->win_cells_sampler = ctx->sampler;
+}
+inline void note_no_window(mvs_ctx *ctx) { ctx->win_planes = 0; }
+// mvs_sweep_use_volume is about to hand the packed volume over (ctx->volume_external still says whose it was): the own volume's layout is
+// kept while a caller's is in use and comes back with it; the library has not written the caller's cells
+inline void note_volume_swapped(mvs_ctx *ctx, bool to_external)
+{
+    if (to_external) {
+        if (!ctx->volume_external) ctx->own_cells_sampler = ctx->vol_cells_sampler;
+        ctx->vol_cells_sampler = -1;
+    } else if (ctx->volume_external) {
+        ctx->vol_cells_sampler = ctx->own_cells_sampler;
+    }
+}
 // select.hip: MVS_ESTATE when cells written under `cells_sampler` (-1: unknown, readable) would be decoded in the current sampler's layout,
 // or when they are a mixture of both layouts (CELLS_MIXED)
 int cells_readable(mvs_ctx *ctx, const char *who, const char *what, int cells_sampler);

@@ -34,8 +34,6 @@
 
 namespace mvs {
 
-int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the 32 x 32 weight table on the device
-
 namespace {
 
 constexpr int PR_KEPT = 0, PR_NEAR = 1, PR_FAR = 2, PR_RANDOM = 3;
@@ -428,18 +426,12 @@ int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int 
     static const char who[] = "mvs_propagate_init";
     if (!ctx) return fail(nullptr, MVS_EINVAL, "%s: null context", who);
     if (!depth_dev) return fail(ctx, MVS_EINVAL, "%s: depth_dev is null", who);
-    if (cost != MVS_COST_ABSDIFF && cost != MVS_COST_ZNCC) return fail(ctx, MVS_EINVAL, "%s: unknown cost %d", who, cost);
-    const int rmin = cost == MVS_COST_ZNCC ? 1 : 0;
-    if (radius < rmin || radius > 4) return fail(ctx, MVS_EINVAL, "%s: radius %d outside %d..4", who, radius, rmin);
-    if (keep < 0 || keep > 8) return fail(ctx, MVS_EINVAL, "%s: keep %d outside 1..8 and not MVS_KEEP_ALL", who, keep);
+    int rc;
+    if ((rc = bestk_arguments(ctx, who, cost, radius, keep))) return rc;
     if (flags & ~MVS_PROPAGATE_SLOPES) return fail(ctx, MVS_EINVAL, "%s: unknown flag bits 0x%x (MVS_PROPAGATE_SLOPES only)", who, flags & ~MVS_PROPAGATE_SLOPES);
     if (!(max_step >= 0.0f)) return fail(ctx, MVS_EINVAL, "%s: max_step %g is negative or NaN", who, (double)max_step);
-    int rc;
     if ((rc = staged_state(ctx, who))) return rc;
-    if (view_first < 0 || view_count < 0 || view_first + view_count > ctx->V)
-        return fail(ctx, MVS_EINVAL, "%s: view range [%d,%d) outside 0..%d", who, view_first, view_first + view_count, ctx->V);
-    if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler's cells hold at most 255 views (have %d)", who, ctx->V);
-    if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler addresses images of up to 16383 x 16383", who);
+    if ((rc = fx_sampler_limits(ctx, who, view_first, view_count))) return rc;
     PropGeo tab = {};
     if (ctx->prop_cons_n > 0 && (rc = consistency_stage(ctx, who, keep, view_count, tab))) return rc;
     MVS_HIP(ctx, hipSetDevice(ctx->device));

@@ -606,15 +606,13 @@ int mvs_sweep_use_volume(mvs_ctx *ctx, void *device_ptr, size_t bytes)
 {
     if (!ctx) return MVS_EINVAL;
     MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    note_volume_swapped(ctx, device_ptr != nullptr);
     if (!device_ptr) {
-        if (ctx->volume_external) ctx->vol_cells_sampler = ctx->own_cells_sampler;
         ctx->volume_external = false;
         ctx->volume = (uint32_t *)ctx->volume_own.ptr;
         ctx->volume_bytes = ctx->volume_own.bytes;
         return MVS_OK;
     }
-    if (!ctx->volume_external) ctx->own_cells_sampler = ctx->vol_cells_sampler;
-    ctx->vol_cells_sampler = -1;   // the caller's cells: the library has not written them
     ctx->volume_external = true;
     ctx->volume = (uint32_t *)device_ptr;
     ctx->volume_bytes = bytes;
@@ -863,15 +861,8 @@ static int sweep_run_impl(mvs_ctx *ctx, const SweepRange &r, unsigned flags)
     if (r.row_count <= 0 || r.plane_count <= 0) return MVS_OK;  // empty band or empty plane group: nothing to compute
     note_ordinary_sweep(ctx);
     rc = ctx->sampler == MVS_SAMPLER_FIXED ? sweep_run_fixed(ctx, r, f) : sweep_run_exact(ctx, r, f);
-    if (rc == MVS_OK && f.vol) {
-        // a row band or a plane group writes part of the volume: under another sampler than the rest was written with, the volume holds
-        // cells of both layouts until a sweep writes all of it
-        const bool whole = r.row_first <= 0 && r.row_first + r.row_count >= ctx->H && r.plane_first <= 0 && r.plane_first + r.plane_count >= ctx->D;
-        if (whole || ctx->vol_cells_sampler == -1 || ctx->vol_cells_sampler == ctx->sampler)
-            note_volume_written(ctx);
-        else
-            ctx->vol_cells_sampler = mvs_ctx::CELLS_MIXED;
-    }
+    if (rc == MVS_OK && f.vol)
+        note_volume_part_written(ctx, r.row_first <= 0 && r.row_first + r.row_count >= ctx->H && r.plane_first <= 0 && r.plane_first + r.plane_count >= ctx->D);
     if (rc == MVS_OK && f.fused) note_rows_selected(ctx, r.row_first, r.row_first + r.row_count);
     return rc;
 }

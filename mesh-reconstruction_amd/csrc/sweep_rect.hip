@@ -855,7 +855,6 @@ __global__ __launch_bounds__(256, RX_WAVES_PER_SIMD) void sweep_fx_rect(RectArgs
 // ------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------
-int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip
 
 bool rect_view_host(const float *q) { return q[1] == 0.0f && q[4] == 0.0f && q[8] == 0.0f && q[9] == 0.0f && q[10] == 0.0f && q[11] > 0.0f; }
 

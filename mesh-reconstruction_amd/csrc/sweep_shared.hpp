@@ -1,7 +1,8 @@
 // sweep_shared.hpp -- what the two sweep samplers (sweep.hip: exact f32, contract v1; sweep_fx.hip: fixed point, contract v2)
 // have in common: launch parameters, the projective arithmetic up to s and r = RN(1/s.w), the XCD-aware tile order, and the host-side
-// decisions every sweep entry makes alike (outputs, cell layout, the fixed-point entries' preconditions).  The packed cells and the rules
-// of depth selection are select_rules.hpp's.
+// decisions every sweep entry makes alike (outputs, cell layout) and the one body of the fixed-point entries beside mvs_sweep_run --
+// the ZNCC, best-K, band, band best-K and gated sweeps: fx_sweep_run, with their preconditions and the sampler's limits.  The packed cells
+// and the rules of depth selection are select_rules.hpp's; the state the body leaves is mvs_internal.hpp's note_fx_sweep.
 #pragma once
 #include "mvs_internal.hpp"
 #include "select_rules.hpp"
@@ -290,8 +291,19 @@ inline int sweep_outputs(mvs_ctx *ctx, bool need_volume, const char *who)
     return MVS_OK;
 }
 
-// host: what mvs_sweep_run_band and mvs_sweep_run_zncc (`who`) check alike before they touch anything: the flag bits, the inputs, the
-// sampler and its limits, the view range.  Decodes the two output flags.
+// host: the fixed sampler's limits as every stage that samples with it (`who`) refuses them: the view range, the views a cell counts, the
+// image size its addresses reach
+inline int fx_sampler_limits(mvs_ctx *ctx, const char *who, int view_first, int view_count)
+{
+    if (view_first < 0 || view_count < 0 || view_first + view_count > ctx->V)
+        return fail(ctx, MVS_EINVAL, "%s: view range [%d,%d) outside 0..%d", who, view_first, view_first + view_count, ctx->V);
+    if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler's cells hold at most 255 views (have %d)", who, ctx->V);
+    if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler addresses images of up to 16383 x 16383", who);
+    return MVS_OK;
+}
+
+// host: what the fixed-sampler sweep entries (`who`) check alike before they touch anything: the flag bits, the inputs, the sampler and
+// its limits.  Decodes the two output flags.
 inline int fx_sweep_preconditions(mvs_ctx *ctx, const char *who, int view_first, int view_count, unsigned flags, bool &vol, bool &fused)
 {
     if (flags & ~(MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN))
@@ -302,11 +314,7 @@ inline int fx_sweep_preconditions(mvs_ctx *ctx, const char *who, int view_first,
     if (!vol && !fused) return fail(ctx, MVS_EINVAL, "%s: flags select neither volume nor fused argmin", who);
     if (!ctx->have_main || !ctx->have_views || !ctx->have_planes) return fail(ctx, MVS_ESTATE, "%s: set main view, side views and planes first", who);
     if (ctx->sampler != MVS_SAMPLER_FIXED) return fail(ctx, MVS_ESTATE, "%s: implemented for MVS_SAMPLER_FIXED (the library default)", who);
-    if (view_first < 0 || view_count < 0 || view_first + view_count > ctx->V)
-        return fail(ctx, MVS_EINVAL, "%s: view range [%d,%d) outside 0..%d", who, view_first, view_first + view_count, ctx->V);
-    if (ctx->V > 255) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler's cells hold at most 255 views (have %d)", who, ctx->V);
-    if (ctx->W > 16383 || ctx->H > 16383) return fail(ctx, MVS_EINVAL, "%s: the fixed sampler addresses images of up to 16383 x 16383", who);
-    return MVS_OK;
+    return fx_sampler_limits(ctx, who, view_first, view_count);
 }
 
 // host: narrows filled parameters to planes [plane_first, +plane_count) and rows [row_first, +row_count), in the units of the shape
@@ -359,6 +367,48 @@ inline auto with_cells(const mvs_ctx *ctx, F &&f)
 {
     if (ctx->sampler == MVS_SAMPLER_FIXED) return f(std::integral_constant<int, CS_FIXED>{});
     return f(std::integral_constant<int, CS_EXACT>{});
+}
+
+int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the fixed sampler's 32 x 32 weight table on the device (ctx->fx_lut)
+
+// One call of a fixed-sampler sweep entry (the ZNCC, best-K, band, band best-K and gated sweeps) whose own arguments are checked
+struct FxSweepCall {
+    const char *who;
+    int view_first, view_count;
+    unsigned flags;
+    const void *prior_dev;  // non-null: a band run, plane d of pixel p is prior(p) + the plane table's delta_d
+    int tile_h, pc;         // the kernel's tile height and planes per chunk (fill_params)
+};
+
+// host: the body of those entries, what tests/shadow_context.py states as _fx_sweep: refusals, then allocations, then the band's copy of
+// the prior, then launch(p, lut, prior, vol, fused) -- `prior` the context's copy, null without a band --, then the state (note_fx_sweep)
+template <class F>
+inline int fx_sweep_run(mvs_ctx *ctx, const FxSweepCall &c, F &&launch)
+{
+    const bool band = c.prior_dev != nullptr;
+    bool vol, fused;
+    int rc;
+    if ((rc = fx_sweep_preconditions(ctx, c.who, c.view_first, c.view_count, c.flags, vol, fused))) return rc;
+    for (int d = 0; band && d < ctx->D; d++)
+        if (!(ctx->z_host[d] > -1.0f && ctx->z_host[d] < 1.0f))
+            return fail(ctx, MVS_ESTATE, "%s: the plane table holds the band's offsets and must lie inside (-1, 1): offset %d is %g", c.who, d, ctx->z_host[d]);
+    MVS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)ctx->W * ctx->H;
+    if ((rc = sweep_outputs(ctx, vol, c.who))) return rc;
+    if (band && (rc = ensure(ctx, ctx->band_prior, P * sizeof(float)))) return rc;
+    if ((rc = ensure_fx_lut(ctx))) return rc;
+    // the context's own copy: the caller's map may be the depth map this run overwrites (stream order puts the copy first)
+    if (band && c.prior_dev != ctx->band_prior.ptr)
+        MVS_HIP(ctx, hipMemcpyAsync(ctx->band_prior.ptr, c.prior_dev, P * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    SweepParams p;
+    fill_params(ctx, p, c.view_first, c.view_count, c.tile_h, c.pc);
+    {
+        ProfileScope ps(ctx, MVS_K_SWEEP);
+        launch(p, (const uint32_t *)ctx->fx_lut.ptr, band ? (const float *)ctx->band_prior.ptr : nullptr, vol, fused);
+    }
+    MVS_HIP(ctx, hipGetLastError());
+    note_fx_sweep(ctx, band, vol, fused);
+    return MVS_OK;
 }
 
 // the launchers: `p` carries the view / plane / row ranges; each chooses its plane split; the caller merges the partial bests

@@ -299,7 +299,7 @@ int mvs_sweep_window(mvs_ctx *ctx, int radius, int tau, const void *guide_dev, u
             }
         }
         ctx->win_vol = larger;
-        ctx->win_planes = 0;   // no Wv until this call's launch is queued
+        note_no_window(ctx);   // no Wv until this call's launch is queued
     }
     WindowArgs a;
     a.vol = ctx->volume;
@@ -324,8 +324,7 @@ int mvs_sweep_window(mvs_ctx *ctx, int radius, int tau, const void *guide_dev, u
     default: launch_window<4>(ctx, gated, a); break;
     }
     MVS_HIP(ctx, hipGetLastError());
-    ctx->win_planes = D;
-    ctx->win_cells_sampler = ctx->sampler;
+    note_window_written(ctx);
     if (select) note_full_selection(ctx);
     return MVS_OK;
 }

@@ -24,8 +24,6 @@
 
 namespace mvs {
 
-int ensure_fx_lut(mvs_ctx *ctx);  // sweep_fx.hip: the 32 x 32 weight table on the device
-
 namespace {
 
 // (the tile's constants, ZnShape, zncc_sample and zncc_cell are sweep_shared.hpp's: bestk.hip shares them)
@@ -148,26 +146,13 @@ int mvs_sweep_run_zncc(mvs_ctx *ctx, int view_first, int view_count, int radius,
 {
     if (!ctx) return fail(nullptr, MVS_EINVAL, "mvs_sweep_run_zncc: null context");
     if (radius < 1 || radius > 4) return fail(ctx, MVS_EINVAL, "mvs_sweep_run_zncc: radius %d outside 1..4", radius);
-    bool vol, fused;
-    int rc;
-    if ((rc = fx_sweep_preconditions(ctx, "mvs_sweep_run_zncc", view_first, view_count, flags, vol, fused))) return rc;
-    MVS_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = sweep_outputs(ctx, vol, "mvs_sweep_run_zncc"))) return rc;
-    if ((rc = ensure_fx_lut(ctx))) return rc;
-    SweepParams p;
-    fill_params(ctx, p, view_first, view_count, ZN_TH, ZN_PC);
-    {
-        ProfileScope ps(ctx, MVS_K_SWEEP);
-        switch (radius) {
-        case 1: zncc_launch<1>(ctx, p, vol, fused); break;
-        case 2: zncc_launch<2>(ctx, p, vol, fused); break;
-        case 3: zncc_launch<3>(ctx, p, vol, fused); break;
-        default: zncc_launch<4>(ctx, p, vol, fused); break;
-        }
-    }
-    MVS_HIP(ctx, hipGetLastError());
-    note_ordinary_sweep(ctx);
-    if (vol) note_volume_written(ctx);
-    fused ? note_full_selection(ctx) : note_no_selection(ctx);
-    return MVS_OK;
+    return fx_sweep_run(ctx, {"mvs_sweep_run_zncc", view_first, view_count, flags, nullptr, ZN_TH, ZN_PC},
+                        [&](const SweepParams &p, const uint32_t *, const float *, bool vol, bool fused) {
+                            switch (radius) {
+                            case 1: zncc_launch<1>(ctx, p, vol, fused); break;
+                            case 2: zncc_launch<2>(ctx, p, vol, fused); break;
+                            case 3: zncc_launch<3>(ctx, p, vol, fused); break;
+                            default: zncc_launch<4>(ctx, p, vol, fused); break;
+                            }
+                        });
 }

@@ -1,39 +1,12 @@
 """Resources of the appearance kernels (csrc/tsdf.hip, csrc/appearance.hip) from the compiler's report for gfx950 with the Makefile's own
 CXXFLAGS: no scratch, no spills and at most 96 VGPRs, and the kernels of mvs_tsdf_integrate, whose bodies the new
 ones share, keep the figures of DESIGN.md section 12's table."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from test_rect_resources_cpu import HIPCC, PKG, _makefile_flags
+from kernel_resources import fixture
 
 
-def _report(tmp, source):
-    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library"
-    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", source), "-o", str(tmp / (source + ".o")),
-                                                      "-Rpass-analysis=kernel-resource-usage"], cwd=PKG, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        if "remark:" not in line or "[-Rpass-analysis" not in line:
-            continue
-        key, _, val = line.split("remark:", 1)[1].rsplit("[-Rpass-analysis", 1)[0].strip().rpartition(":")
-        if key.strip() == "Function Name":
-            cur = kernels.setdefault(val.strip(), {})
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return kernels
-
-
-@pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("appearance")
-    kernels = _report(tmp, "tsdf.hip")
-    kernels.update(_report(tmp, "appearance.hip"))
-    return kernels
+resources = fixture("tsdf.hip", "appearance.hip")
 
 
 def _one(resources, kernel):

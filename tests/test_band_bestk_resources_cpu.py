@@ -3,35 +3,16 @@ Makefile's own CXXFLAGS: 36 instantiations, as on the plane table -- (five radii
 four list sizes KMAX = 0 (MVS_KEEP_ALL), 2, 4, 8 -- none with scratch or spills.  Registers, occupancy and LDS are
 printed: the per-sample plane costs NS x 2 vector registers over the table's instantiation."""
 import os
-import shutil
-import subprocess
 
 import pytest
 
-from test_rect_resources_cpu import HIPCC, PKG, _makefile_flags
+from kernel_resources import PKG, fixture
 
 ABSDIFF, ZNCC = 0, 1
 INSTANCES = [(cost, r, kmax) for cost, radii in ((ABSDIFF, (0, 1, 2, 3, 4)), (ZNCC, (1, 2, 3, 4))) for r in radii for kmax in (0, 2, 4, 8)]
 
 
-@pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library"
-    out = str(tmp_path_factory.mktemp("band_bestk") / "band_bestk.o")
-    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", "bestk.hip"), "-o", out,
-                                                      "-Rpass-analysis=kernel-resource-usage"], cwd=PKG, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        if "remark:" not in line or "[-Rpass-analysis" not in line:
-            continue
-        key, _, val = line.split("remark:", 1)[1].rsplit("[-Rpass-analysis", 1)[0].strip().rpartition(":")
-        if key.strip() == "Function Name":
-            cur = kernels.setdefault(val.strip(), {})
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return kernels
+resources = fixture("bestk.hip")
 
 
 def test_every_kernel_of_the_file_is_listed(resources):

@@ -5,10 +5,9 @@ inspection: mvs_propagate_set_consistency allocates nothing, the stage still has
 term's checks sit in front of them."""
 import os
 
-import pytest
 
+from kernel_resources import PKG
 from test_propagate_resources_cpu import INSTANCES, resources  # noqa: F401  (the fixture: one compilation of the file per module)
-from test_rect_resources_cpu import PKG
 
 KEYS = ("VGPRs", "TotalSGPRs", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill")
 

@@ -5,13 +5,11 @@ and no spills in any instantiation (four radii, gated by a guide or not, median 
 import glob
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 import mvs_amd
-from test_rect_resources_cpu import HIPCC, PKG, _makefile_flags
+from kernel_resources import PKG, fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # depth_filter_median<R, GATED>, depth_filter_mean<R, GATED>
@@ -51,24 +49,7 @@ def test_nothing_is_allocated_without_a_call():
     assert body.count("dfilter_have = true") == 1 and body.index("dfilter_have = true") > body.index("ensure(ctx, ctx->dfilter_maps")
 
 
-@pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library"
-    out = str(tmp_path_factory.mktemp("depth_filter") / "depth_filter.o")
-    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", "depth_filter.hip"), "-o", out,
-                                                      "-Rpass-analysis=kernel-resource-usage"], cwd=PKG, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        if "remark:" not in line or "[-Rpass-analysis" not in line:
-            continue
-        key, _, val = line.split("remark:", 1)[1].rsplit("[-Rpass-analysis", 1)[0].strip().rpartition(":")
-        if key.strip() == "Function Name":
-            cur = kernels.setdefault(val.strip(), {})
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return kernels
+resources = fixture("depth_filter.hip")
 
 
 def test_every_kernel_of_the_file_is_listed(resources):

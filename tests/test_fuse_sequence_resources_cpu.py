@@ -5,12 +5,9 @@ table is this output).  And by source inspection: the support buffer is allocate
 mvs_fuse_sequence behind its last refusal, and that call synchronises the stream exactly once when no rows are downloaded."""
 import os
 import re
-import shutil
-import subprocess
 
-import pytest
 
-from test_rect_resources_cpu import HIPCC, PKG, _makefile_flags
+from kernel_resources import PKG, fixture
 
 KEYS = ("VGPRs", "TotalSGPRs", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill")
 FUSE = ("fuse_count_kernel", "fuse_rows_kernel", "fuse_count_masked_kernel", "fuse_rows_masked_kernel")
@@ -18,31 +15,7 @@ SEQUENCE = ("fuse_seq_count_kernel", "fuse_seq_rows_kernel", "fuse_seq_advance_k
 BEFORE = {"fuse_count_kernel": 26, "fuse_rows_kernel": 30}   # VGPRs, DESIGN.md section 11
 
 
-def _report(tmp, name):
-    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library"
-    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", name), "-o", str(tmp / (name + ".o")),
-                                                      "-Rpass-analysis=kernel-resource-usage"], cwd=PKG, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        if "remark:" not in line or "[-Rpass-analysis" not in line:
-            continue
-        key, _, val = line.split("remark:", 1)[1].rsplit("[-Rpass-analysis", 1)[0].strip().rpartition(":")
-        if key.strip() == "Function Name":
-            cur = kernels.setdefault(val.strip(), {})
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return kernels
-
-
-@pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    tmp = tmp_path_factory.mktemp("fuse_sequence")
-    out = {}
-    for name in ("fuse.hip", "fuse_sequence.hip"):
-        out.update(_report(tmp, name))
-    return out
+resources = fixture("fuse.hip", "fuse_sequence.hip")
 
 
 def _ours(resources, kernel):

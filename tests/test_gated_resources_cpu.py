@@ -4,36 +4,17 @@ or spills.  Registers, occupancy and LDS are printed.  An
 what mvs_sweep_run_bestk allocates, behind every argument check, and nothing else in the library knows of it."""
 import glob
 import os
-import shutil
-import subprocess
 
 import pytest
 
-from test_rect_resources_cpu import HIPCC, PKG, _makefile_flags
+from kernel_resources import PKG, fixture
 
 ABSDIFF, ZNCC = 0, 1
 INSTANCES = [(cost, r, kmax) for cost in (ABSDIFF, ZNCC) for r in (1, 2, 3, 4) for kmax in (0, 2, 4, 8)]
 SOURCE = os.path.join(PKG, "csrc", "bestk_gated.hip")
 
 
-@pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library"
-    out = str(tmp_path_factory.mktemp("bestk_gated") / "bestk_gated.o")
-    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", "bestk_gated.hip"), "-o", out,
-                                                      "-Rpass-analysis=kernel-resource-usage"], cwd=PKG, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        if "remark:" not in line or "[-Rpass-analysis" not in line:
-            continue
-        key, _, val = line.split("remark:", 1)[1].rsplit("[-Rpass-analysis", 1)[0].strip().rpartition(":")
-        if key.strip() == "Function Name":
-            cur = kernels.setdefault(val.strip(), {})
-        elif cur is not None:
-            cur[key.strip()] = val.strip()
-    return kernels
+resources = fixture("bestk_gated.hip")
 
 
 def test_every_kernel_of_the_file_is_listed(resources):
@@ -51,15 +32,20 @@ def test_no_scratch_and_no_spills(resources, cost, r, kmax):
 
 
 def test_only_the_entrys_own_path_allocates():
-    """the entry makes what mvs_sweep_run_bestk makes (the maps, the volume of a volume run, the weight table) through the shared helpers,
-    behind its last refusal; it has no buffer of its own on the context, and the sweeps it is not to touch do not name it"""
+    """the entry makes what mvs_sweep_run_bestk makes (the maps, the volume of a volume run, the weight table) through the one body of the fixed-sampler
+    entries (fx_sweep_run), behind its last refusal and behind the shared ones; it has no buffer of its own on the context, and the sweeps it is not to touch do not name it"""
     src = open(SOURCE).read()
     assert src.count("hipMalloc") == 0 and src.count("ensure(") == 0 and src.count("DevBuf") == 0
     body = src[src.index("int mvs_sweep_run_bestk_gated("):]
-    first = min(body.index("sweep_outputs("), body.index("ensure_fx_lut("))
-    assert body.rindex("return fail(") < first and body.index("fx_sweep_preconditions(") < first     # every check comes first
+    assert body.count("fx_sweep_run(") == 1
+    run = body.index("fx_sweep_run(")
+    assert body.rindex("return fail(") < run                                                          # every check of its own comes first
     for check in ("null context", "unknown cost", "radius %d outside 1..4", "keep %d outside", "tau %d outside 0..255"):
-        assert check in body[:first], check
+        assert check in body[:run], check
+    shared = open(os.path.join(PKG, "csrc", "sweep_shared.hpp")).read()
+    shared = shared[shared.index("inline int fx_sweep_run("):]
+    shared = shared[:shared.index("\n}\n")]
+    assert shared.index("fx_sweep_preconditions(") < min(shared.index("sweep_outputs("), shared.index("ensure("), shared.index("ensure_fx_lut("))
     users = sorted(os.path.basename(p) for p in glob.glob(os.path.join(PKG, "csrc", "*")) if "bestk_gated" in open(p, errors="replace").read())
     assert users == ["bestk_gated.hip"], users          # no state of the sweep's on the context, no caller inside the library
 

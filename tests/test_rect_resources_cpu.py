@@ -4,17 +4,10 @@ per SIMD (<= 96 VGPRs).  The spills are bounded at what the clean region body le
 none -- but a ratchet, so that an edit cannot make them worse unnoticed.  Before that body the headline instantiation spilled 21 SGPRs
 (now 28, 29 at RS 64) and the volume-only one 28 (now 52, 58 at RS 64); the spill code sits in the chunk epilogue and the
 failed-certificate block, not on the clean path."""
-import os
-import re
-import shlex
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "mesh-reconstruction_amd")
-HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+from kernel_resources import fixture
+
 RS_ALL = (64, 84, 96, 128)
 
 # per instantiation (WRITE_VOLUME, FUSED): at most this many VGPRs, at least this many waves per SIMD, at most this much scratch
@@ -26,33 +19,7 @@ BOUNDS = {
 }
 
 
-def _makefile_flags():
-    """CXXFLAGS as mesh-reconstruction_amd/Makefile sets them (the build that ships)"""
-    text = open(os.path.join(PKG, "Makefile")).read()
-    m = re.search(r"^CXXFLAGS\s*\?=\s*(.*)$", text, re.M)
-    assert m, "no CXXFLAGS line in the Makefile"
-    return shlex.split(m.group(1).replace("$(ARCH)", "gfx950"))
-
-
-@pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
-    assert hipcc, "hipcc is needed to build the library"
-    out = str(tmp_path_factory.mktemp("rect") / "sweep_rect.o")
-    r = subprocess.run([hipcc] + _makefile_flags() + ["--cuda-device-only", "-c", os.path.join("csrc", "sweep_rect.hip"), "-o", out,
-                                          "-Rpass-analysis=kernel-resource-usage"], cwd=PKG, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+([^:]+?):\s+(\S+)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        key, val = m.group(1).strip(), m.group(2)
-        if key == "Function Name":
-            cur = kernels.setdefault(val, {})
-        elif cur is not None:
-            cur[key] = val
-    return kernels
+resources = fixture("sweep_rect.hip")
 
 
 @pytest.mark.parametrize("inst", sorted(BOUNDS), ids=lambda i: "vol%d_fused%d" % i)

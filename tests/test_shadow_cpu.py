@@ -212,3 +212,26 @@ def test_a_plane_group_under_the_other_sampler_is_read_by_nobody():
     s = sc.replay("crafted", sc.prologue("crafted") + [("set_sampler", "exact"), ("sweep_run_planes", 0, 3, 0, 19, VOLUME)])
     assert s.history[-1][-1] == OK and s.own_cells == "exact"
     assert s.call("sweep_run_planes", 0, 3, 0, 8, VOLUME) == sc.EINVAL and s.call("sweep_run_planes", 0, 3, 0, 19, BOTH) == sc.EINVAL
+
+
+def test_the_tabulated_state_is_assigned_by_the_named_transitions_only():
+    """section 30's state changes in mvs_internal.hpp (the fields' initialisers and the note_* transitions) and in note_rows_selected
+    (select.hip), nowhere else in csrc"""
+    import glob
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mesh-reconstruction_amd", "csrc")
+    fields = "sel_planes sel_band_planes sel_band_lo sel_band_hi band_planes band_resolved vol_cells_sampler own_cells_sampler win_cells_sampler win_planes".split()
+    assigned = re.compile(r"\b(%s)\s*([-+*/|&^]?=(?!=)|\+\+|--)" % "|".join(fields))
+    found = []
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        text = open(path, errors="replace").read()
+        if os.path.basename(path) == "mvs_internal.hpp":
+            assert len(assigned.findall(text)) >= len(fields)       # the check sees assignments where they are
+            continue
+        if os.path.basename(path) == "select.hip":
+            m = re.search(r"^void note_rows_selected\(.*?^}\n", text, re.M | re.S)
+            assert m and assigned.search(m.group(0))
+            text = text.replace(m.group(0), "")
+        found += ["%s: %s" % (os.path.basename(path), line.strip()) for line in text.splitlines() if assigned.search(line)]
+    assert not found, found

@@ -64,6 +64,21 @@ def test_plane_group_under_the_other_sampler(reader):
         device.close()
 
 
+@pytest.mark.parametrize("writer", ["zncc_volume", "bestk_volume", "gated_volume", "band_volume", "band_bestk_volume"])
+def test_a_fixed_sampler_entry_rewrites_an_exact_volume(writer):
+    """the volume was last written under the exact sampler; one of the fixed sampler's other entries then writes all of it: the cells
+    are the fixed layout's and every reader takes them.  The matrix does not see this: its baseline volume has the fixed layout already,
+    and a missing note_volume_written in these entries' common epilogue passed all of it"""
+    rewritten = [("set_sampler", "exact"), ("sweep_run", 0, 3, sc.VOLUME), ("set_sampler", "fixed")] + sc.writers("crafted")[writer]
+    shadow, device = _run("crafted", sc.prologue("crafted") + rewritten)
+    try:
+        assert shadow.own_cells == "fixed"
+        sc.compare(shadow, device, "behind the rewrite: ")
+        assert sc.step(shadow, device, *sc.READERS["argmin"]) == OK
+    finally:
+        device.close()
+
+
 @pytest.mark.parametrize("which", sorted(sc.BYSTANDERS))
 def test_bystanders_change_nothing(which):
     """calls of other stages and refused calls leave every fetchable of the family as it was"""
