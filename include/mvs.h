@@ -946,6 +946,52 @@ int mvs_fuse_sequence(mvs_ctx *ctx, int nrefs, const int *ref_slots, int nneighb
                       float *out_points7 /* nullable: max_rows x 7 */, int *out_ref_counts /* nullable: nrefs */, long long *out_count);
 void *mvs_fuse_sequence_points_device(mvs_ctx *ctx); /* the rows of the last call, min(total, max_rows) of them; NULL before the first */
 
+/* ---- normals: from the propagation's slopes, per depth slot, in the fusion (csrc/normals.hip) ----------------
+ * A normal map is H * W * 3 f32, interleaved, unit; (0, 0, 0) means none -- the layout of mvs_tsdf_raycast_normals_device.  All
+ * arithmetic is f32 with one rounding per operation, `/` and sqrt correctly rounded, no FMA but the pixel centres'.
+ *
+ * Rule N1 (mvs_propagate_normals).  cam is the main camera P (row-major, clip = P X) as given to mvs_depth_upload; its centre C is derived
+ * as mvs_depth_slot_matrices derives it.  For pixel (row, col) holding the hypothesis (z, gx, gy) with -1 < z < 1:
+ *   xn, yn   the sweep's pixel centres, fmaf(2 col + 1, 1/W, -1) and fmaf(-(2 row + 1), 1/H, 1)
+ *   a = -gx (W 0.5),  b = gy (H 0.5),  d = -((z + a xn) + b yn)                 the NDC plane a x + b y + z + d = 0
+ *   m_k = ((a P[0][k] + b P[1][k]) + P[2][k]) + d P[3][k],  k = 0..3            its world plane, the row vector times P
+ *   n = m.xyz / sqrt((m0 m0 + m1 m1) + m2 m2)                                    zeros when the length is 0, infinite or NaN
+ *   n is negated when ((m0 C0 + m1 C1) + m2 C2) + m3 < 0                         the normal points to the camera's side of the plane
+ * A pixel without a hypothesis (z outside (-1, 1), NaN) gives zeros.  The call reads the stage's maps as they are at that point of the
+ * stream (after any mvs_propagate_run), is asynchronous and touches no other state; the map is made by the first call, behind every check.
+ * MVS_EINVAL: NULL argument, a camera with a non-finite entry, singular or without a finite centre; MVS_ESTATE: before mvs_propagate_init
+ * (mvs_propagate_normals), before the first mvs_propagate_normals (the fetch; the pointer is NULL then).
+ *
+ * Normal planes.  One plane per depth slot in one buffer of `capacity` planes, made by the first normals upload after mvs_depth_store and
+ * freed by mvs_depth_store.  Uploads are stream-ordered like mvs_depth_upload*; the fetch synchronises.  mvs_depth_upload* into a slot drops
+ * that slot's plane (a flag), so a plane always describes the stored map.  The device form takes mvs_propagate_normals_device(ctx) or
+ * mvs_tsdf_raycast_normals_device(ctx) unchanged.  Errors are the support planes': MVS_EINVAL for a NULL argument or a slot outside the
+ * store, MVS_ESTATE for an upload into a slot without a depth map or a fetch from a slot without a plane, MVS_ENOMEM.
+ * A stored normal is USABLE when 0.5 < (nx nx + ny ny) + nz nz < 2: false for zeros, NaN and infinities.
+ *
+ * mvs_fuse_depth_normals is mvs_fuse_depth_masked (rules 1s-5) with two changes; n_r is the reference slot's stored normal at the pixel,
+ * n_j voter j's stored normal at the pixel (r, c) rule 3 read it at.
+ *   3n  A voter that passes every test of rule 3 must also satisfy (n_r.x n_j.x + n_r.y n_j.y) + n_r.z n_j.z >= min_normal_cos whenever
+ *       both normals are usable; the test passes when either is missing (no plane on that slot, or an unusable value).
+ *       min_normal_cos <= 1; -INFINITY turns the test off; NaN or a value above 1 is MVS_EINVAL.
+ *   5n  When n_r is usable the pixel is not subject to the tangent rule (it is not dropped for lacking neighbours); the row's normal is
+ *       n_r plus the usable n_j of the agreeing voters, added componentwise in listed order, divided by its length
+ *       sqrt((sx sx + sy sy) + sz sz) (0 or infinite: the pixel is dropped) and turned toward C_r by rule 5's own test.  Otherwise rule 5
+ *       stands as it is.
+ * No plane in the store and -INFINITY give mvs_fuse_depth_masked's bytes, planes of zeros too, and with min_support = 0 mvs_fuse_depth's.
+ * Rows land in the buffer mvs_fuse_points_device returns.
+ * Out of scope: mvs_fuse_sequence with normals, TSDF weights from normals, normals for the band and plane-table sweeps, the exact sampler,
+ * the C++ seam (host/recon.hpp). */
+int mvs_propagate_normals(mvs_ctx *ctx, const float cam[16]);
+void *mvs_propagate_normals_device(mvs_ctx *ctx); /* H*W*3 f32; NULL before the first mvs_propagate_normals */
+int mvs_propagate_normals_fetch(mvs_ctx *ctx, float *normals_hw3);
+int mvs_depth_normals_upload(mvs_ctx *ctx, int slot, const float *normals_hw3);
+int mvs_depth_normals_upload_device(mvs_ctx *ctx, int slot, const void *normals_dev);
+int mvs_depth_normals_fetch(mvs_ctx *ctx, int slot, float *normals_hw3);
+int mvs_depth_normals_drop(mvs_ctx *ctx, int slot);
+int mvs_fuse_depth_normals(mvs_ctx *ctx, int ref_slot, int nneighbours, const int *neighbour_slots, int min_consistent, float max_reproj_px,
+                           float max_rel_depth, float max_cost, int min_support, float min_normal_cos, float *out_points7, int *out_count);
+
 /* ---- one main view on several GPUs of one node (SURVEY.md section 8b "multi-GPU", 8e, north_star) -----------------------------
  * A communicator owns one context per listed device and one RCCL communicator across them (librccl is loaded when the first
  * communicator is created; the library has no link dependency on it).  mvs_sweep_sharded runs ONE main view on all of them, one host

@@ -273,7 +273,7 @@ void mvs_destroy(mvs_ctx *ctx)
                       &ctx->r_shadow, &ctx->r_frame, &ctx->r_out3, &ctx->r_tmp0, &ctx->r_tmp1, &ctx->r_tmp2,
                       &ctx->cubic_tab, &ctx->flow_arena, &ctx->frame_buf, &ctx->best_parts, &ctx->plan_stats, &ctx->probe_buf, &ctx->filter_sort, &ctx->raster_bins, &ctx->fx_lut, &ctx->side_quads, &ctx->side_quads16,
                       &ctx->r_mips, &ctx->flow_batch_arena, &ctx->rect_tab, &ctx->r_tris_main, &ctx->store_raw, &ctx->store_quads, &ctx->batch_slot[0].buf, &ctx->batch_slot[1].buf, &ctx->frame_ptrs, &ctx->view_slots, &ctx->xrect_tab, &ctx->sep_tab,
-                      &ctx->dstore_depth, &ctx->dstore_cost, &ctx->fuse_rows, &ctx->fuse_counts, &ctx->fuse_scan, &ctx->dstore_support, &ctx->fuse_seq_rows, &ctx->fuse_seq_claims, &ctx->fuse_seq_state,
+                      &ctx->dstore_depth, &ctx->dstore_cost, &ctx->fuse_rows, &ctx->fuse_counts, &ctx->fuse_scan, &ctx->dstore_support, &ctx->store_normals, &ctx->hyp_normals, &ctx->fuse_seq_rows, &ctx->fuse_seq_claims, &ctx->fuse_seq_state,
                       &ctx->tsdf_vol, &ctx->tsdf_wmaps, &ctx->tsdf_work, &ctx->tsdf_bricks, &ctx->ray_depth, &ctx->ray_normals, &ctx->agg_cost, &ctx->agg_sum,
                       &ctx->clean_labels, &ctx->clean_sizes, &ctx->clean_counters, &ctx->win_vol, &ctx->band_prior, &ctx->band_depth, &ctx->band_counters,
                       &ctx->tsdf_app, &ctx->shade_map, &ctx->app_points, &ctx->lens_stage, &ctx->pyr_frames, &ctx->filter_density, &ctx->prop_maps, &ctx->prop_counters,

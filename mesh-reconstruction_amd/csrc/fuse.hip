@@ -28,30 +28,7 @@ namespace mvs {
 
 namespace {
 
-// WRITE = false: keep count per segment (row * ntx + tile column) and counts[H * ntx] = 0; WRITE = true: rows at the scanned offsets.
-// A = FuseArgs: mvs_fuse_depth; A = FuseMaskedArgs: mvs_fuse_depth_masked with min_support > 0 (rule 1s)
-template <bool WRITE, class A>
-__device__ __forceinline__ void fuse_body(const A &a, int *__restrict__ counts, const int *__restrict__ offsets, float *__restrict__ rows)
-{
-    __shared__ float4 tile[kFuseTY + 2][kFuseTX + 2];
-    const int tx = threadIdx.x & (kFuseTX - 1), ty = threadIdx.x / kFuseTX;
-    const int col0 = blockIdx.x * kFuseTX, row0 = blockIdx.y * kFuseTY;
-    fuse_load_tile(a, tile, row0, col0);
-    const int row = row0 + ty, col = col0 + tx;
-    float out[7];
-    unsigned agreed;
-    const bool keep = row < a.H && col < a.W && fuse_pixel(a, tile, ty + 1, tx + 1, row, col, out, agreed);
-    const unsigned long long m = __ballot(keep);
-    const int seg = row * a.ntx + blockIdx.x;
-    if (!WRITE) {
-        if (tx == 0 && row < a.H) counts[seg] = __popcll(m);
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) counts[a.H * a.ntx] = 0;
-    } else if (keep) {
-        float *dst = rows + 7 * (size_t)(offsets[seg] + __popcll(m & ((1ull << tx) - 1ull)));
-        for (int k = 0; k < 7; k++) dst[k] = out[k];
-    }
-}
-
+// fuse_body (fuse_rules.hpp) over the two argument blocks of this file
 __global__ __launch_bounds__(256) void fuse_count_kernel(const FuseArgs a, int *__restrict__ counts) { fuse_body<false>(a, counts, nullptr, nullptr); }
 __global__ __launch_bounds__(256) void fuse_rows_kernel(const FuseArgs a, const int *__restrict__ offsets, float *__restrict__ rows)
 {
@@ -110,6 +87,7 @@ int depth_upload_impl(mvs_ctx *ctx, int slot, const float cam[16], const float *
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     ctx->dstore[slot].have = false;
     ctx->dstore[slot].have_support = false;  // a new map is not described by the old plane's bytes
+    ctx->dstore[slot].have_normals = false;  // (nor by the old normals': section 31)
     MVS_HIP(ctx, hipMemcpyAsync((float *)ctx->dstore_depth.ptr + P * slot, depth, P * sizeof(float), kind, ctx->stream));
     if (cost) MVS_HIP(ctx, hipMemcpyAsync((float *)ctx->dstore_cost.ptr + P * slot, cost, P * sizeof(float), kind, ctx->stream));
     s.have = true;
@@ -268,6 +246,11 @@ int mvs_depth_store(mvs_ctx *ctx, int capacity)
         MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         MVS_HIP(ctx, hipFree(ctx->dstore_support.ptr));
         ctx->dstore_support = DevBuf();
+    }
+    if (ctx->store_normals.ptr) {  // and so do the normal planes (section 31)
+        MVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        MVS_HIP(ctx, hipFree(ctx->store_normals.ptr));
+        ctx->store_normals = DevBuf();
     }
     int rc;
     if ((rc = ensure(ctx, ctx->dstore_depth, bytes))) return rc;

@@ -1,8 +1,9 @@
 // fuse_rules.hpp -- the per-pixel contract of the depth-map fusion (include/mvs.h "depth store + fusion", DESIGN.md sections 11 and 28) as
 // device functions: ref_point (rules 1 / 1s and 2 for a reference pixel), tangent (the normal's two axes) and fuse_pixel (rules 3 to 5).
-// Shared by csrc/fuse.hip (mvs_fuse_depth, mvs_fuse_depth_masked) and csrc/fuse_sequence.hip (mvs_fuse_sequence), so that all three compile
-// the same statements.  The functions are templates over the argument block: FuseArgs reads rule 1, FuseMaskedArgs adds the support planes of
-// rule 1s (`if constexpr`: the unmasked kernels hold no trace of them).  f32, one rounding per operation (-ffp-contract=off).
+// Shared by csrc/fuse.hip (mvs_fuse_depth, mvs_fuse_depth_masked), csrc/fuse_sequence.hip (mvs_fuse_sequence) and csrc/normals.hip
+// (mvs_fuse_depth_normals), so that all of them compile the same statements.  The functions are templates over the argument block: FuseArgs
+// reads rule 1, FuseMaskedArgs adds the support planes of rule 1s, FuseNormalArgs the normal planes of rules 3n and 5n (section 31)
+// (`if constexpr`: the kernels of the smaller blocks hold no trace of the larger ones').  f32, one rounding per operation (-ffp-contract=off).
 #pragma once
 
 #include "depth_rules.hpp"
@@ -20,6 +21,7 @@ constexpr int kFuseTX = 64, kFuseTY = 4;  // tile = 4 wave-wide rows
 // them with the same (scalar) loads.  Index 0 is the reference view, 1..K the neighbours in the caller's order.
 struct FuseArgs {
     static constexpr bool kMasked = false;
+    static constexpr bool kNormals = false;
     const float *depth[kFuseMaxNeighbours + 1];
     const float *cost[kFuseMaxNeighbours + 1];  // null unless the cost threshold is finite
     float P[kFuseMaxNeighbours + 1][16];
@@ -35,6 +37,26 @@ struct FuseMaskedArgs : FuseArgs {
     const uint8_t *support[kFuseMaxNeighbours + 1];
     int min_support;
 };
+
+// rules 3n / 5n: the normal plane (H*W*3 f32, interleaved) of every view that has one (null: none) and the least cosine of rule 3n
+struct FuseNormalArgs : FuseMaskedArgs {
+    static constexpr bool kNormals = true;
+    const float *normals[kFuseMaxNeighbours + 1];
+    float min_cos;
+};
+
+// section 31: the stored normal of pixel p of view j and whether it is usable (false for no plane, zeros, NaN and infinities)
+template <class A>
+__device__ __forceinline__ bool stored_normal(const A &a, int j, size_t p, float &x, float &y, float &z)
+{
+    const float *n = a.normals[j];
+    if (!n) return false;
+    x = n[3 * p];
+    y = n[3 * p + 1];
+    z = n[3 * p + 2];
+    const float s = (x * x + y * y) + z * z;
+    return s > 0.5f && s < 2.0f;
+}
 
 // rule 1 / rule 1s for pixel p of view j
 template <class A>
@@ -99,22 +121,32 @@ __device__ __forceinline__ bool fuse_pixel(const A &a, const float4 (*tile)[kFus
     agreed = 0u;
     const float4 c = tile[ty][tx];
     if (!(c.w > 0.f)) return false;
-    // normal from the reference map alone (before the votes: a pixel without one is dropped anyway)
-    float3 tc, tr;
-    if (!tangent(tile[ty][tx - 1], c, tile[ty][tx + 1], a.max_rel, tc)) return false;
-    if (!tangent(tile[ty - 1][tx], c, tile[ty + 1][tx], a.max_rel, tr)) return false;
-    float nx = tc.y * tr.z - tc.z * tr.y;
-    float ny = tc.z * tr.x - tc.x * tr.z;
-    float nz = tc.x * tr.y - tc.y * tr.x;
-    const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
-    if (!(len > 0.f && len < INFINITY)) return false;
-    nx = nx / len;
-    ny = ny / len;
-    nz = nz / len;
-    if ((nx * (a.C[0] - c.x) + ny * (a.C[1] - c.y)) + nz * (a.C[2] - c.z) < 0.f) {
-        nx = -nx;
-        ny = -ny;
-        nz = -nz;
+    float nx, ny, nz;
+    [[maybe_unused]] bool have_nr = false;   // rule 5n: the reference pixel's stored normal is usable (rx, ry, rz)
+    [[maybe_unused]] float rx = 0.f, ry = 0.f, rz = 0.f;
+    if constexpr (A::kNormals) have_nr = stored_normal(a, 0, (size_t)row * a.W + col, rx, ry, rz);
+    if (!have_nr) {
+        // normal from the reference map alone (before the votes: a pixel without one is dropped anyway)
+        float3 tc, tr;
+        if (!tangent(tile[ty][tx - 1], c, tile[ty][tx + 1], a.max_rel, tc)) return false;
+        if (!tangent(tile[ty - 1][tx], c, tile[ty + 1][tx], a.max_rel, tr)) return false;
+        nx = tc.y * tr.z - tc.z * tr.y;
+        ny = tc.z * tr.x - tc.x * tr.z;
+        nz = tc.x * tr.y - tc.y * tr.x;
+        const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
+        if (!(len > 0.f && len < INFINITY)) return false;
+        nx = nx / len;
+        ny = ny / len;
+        nz = nz / len;
+        if ((nx * (a.C[0] - c.x) + ny * (a.C[1] - c.y)) + nz * (a.C[2] - c.z) < 0.f) {
+            nx = -nx;
+            ny = -ny;
+            nz = -nz;
+        }
+    } else {
+        nx = rx;   // the sum of rule 5n starts at n_r
+        ny = ry;
+        nz = rz;
     }
     // votes of the neighbours, in the listed order
     const float3 X = make_float3(c.x, c.y, c.z);
@@ -141,6 +173,15 @@ __device__ __forceinline__ bool fuse_pixel(const A &a, const float4 (*tile)[kFus
         const float du = ur - (float)col, dv = vr - (float)row;
         if (!(du * du + dv * dv <= a.max_reproj2)) continue;
         if (!(fabsf(sw - c.w) / c.w <= a.max_rel)) continue;
+        if constexpr (A::kNormals) {   // rule 3n, then the voter's share of rule 5n's sum
+            float jx, jy, jz;
+            if (have_nr && stored_normal(a, j, p, jx, jy, jz)) {
+                if (!((rx * jx + ry * jy) + rz * jz >= a.min_cos)) continue;
+                nx = nx + jx;
+                ny = ny + jy;
+                nz = nz + jz;
+            }
+        }
         sx = sx + Xj.x;
         sy = sy + Xj.y;
         sz = sz + Xj.z;
@@ -148,6 +189,20 @@ __device__ __forceinline__ bool fuse_pixel(const A &a, const float4 (*tile)[kFus
         agreed |= 1u << (j - 1);
     }
     if (agree < a.min_consistent) return false;
+    if constexpr (A::kNormals) {
+        if (have_nr) {   // rule 5n: the summed normals over their length, turned to the camera by rule 5's test
+            const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
+            if (!(len > 0.f && len < INFINITY)) return false;
+            nx = nx / len;
+            ny = ny / len;
+            nz = nz / len;
+            if ((nx * (a.C[0] - c.x) + ny * (a.C[1] - c.y)) + nz * (a.C[2] - c.z) < 0.f) {
+                nx = -nx;
+                ny = -ny;
+                nz = -nz;
+            }
+        }
+    }
     const float n = (float)(agree + 1);
     out[0] = sx / n;
     out[1] = sy / n;
@@ -169,6 +224,31 @@ __device__ __forceinline__ void fuse_load_tile(const A &a, float4 (*tile)[kFuseT
         tile[er][ec] = (r >= 0 && r < a.H && c >= 0 && c < a.W) ? ref_point(a, r, c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
+}
+
+// One 64 x 4 tile of the order-preserving compaction (fuse.hip's head comment).  WRITE = false: keep count per segment (row * ntx + tile
+// column) and counts[H * ntx] = 0; WRITE = true: rows at the scanned offsets.  A = FuseArgs: mvs_fuse_depth; A = FuseMaskedArgs:
+// mvs_fuse_depth_masked with min_support > 0 (rule 1s); A = FuseNormalArgs: mvs_fuse_depth_normals (rules 3n, 5n)
+template <bool WRITE, class A>
+__device__ __forceinline__ void fuse_body(const A &a, int *__restrict__ counts, const int *__restrict__ offsets, float *__restrict__ rows)
+{
+    __shared__ float4 tile[kFuseTY + 2][kFuseTX + 2];
+    const int tx = threadIdx.x & (kFuseTX - 1), ty = threadIdx.x / kFuseTX;
+    const int col0 = blockIdx.x * kFuseTX, row0 = blockIdx.y * kFuseTY;
+    fuse_load_tile(a, tile, row0, col0);
+    const int row = row0 + ty, col = col0 + tx;
+    float out[7];
+    unsigned agreed;
+    const bool keep = row < a.H && col < a.W && fuse_pixel(a, tile, ty + 1, tx + 1, row, col, out, agreed);
+    const unsigned long long m = __ballot(keep);
+    const int seg = row * a.ntx + blockIdx.x;
+    if (!WRITE) {
+        if (tx == 0 && row < a.H) counts[seg] = __popcll(m);
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) counts[a.H * a.ntx] = 0;
+    } else if (keep) {
+        float *dst = rows + 7 * (size_t)(offsets[seg] + __popcll(m & ((1ull << tx) - 1ull)));
+        for (int k = 0; k < 7; k++) dst[k] = out[k];
+    }
 }
 
 // the host half shared by the three entry points (fuse.hip): the checks of one (reference, neighbours) list against the depth store and

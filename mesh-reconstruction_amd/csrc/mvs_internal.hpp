@@ -184,10 +184,15 @@ struct mvs_ctx {
     struct DepthSlot {
         bool have = false, have_cost = false;
         bool have_support = false;  // the slot's plane of dstore_support describes the stored map (mvs_depth_support_upload; a depth upload clears it)
+        bool have_normals = false;  // the slot's plane of store_normals describes the stored map (mvs_depth_normals_upload; a depth upload clears it)
         float P[16], Pi[16], C[4];
     };
     mvs::DevBuf dstore_depth, dstore_cost;
     mvs::DevBuf dstore_support;  // support planes (section 28): capacity planes of H*W u8, made by the first support upload, freed by mvs_depth_store
+    // normals (normals.hip, section 31): capacity planes of H*W*3 f32 beside the depth store, made by the first normals upload and freed by
+    // mvs_depth_store; the H*W*3 f32 map of the last mvs_propagate_normals, made by its first call (hyp_normals_have: one has run)
+    mvs::DevBuf store_normals, hyp_normals;
+    bool hyp_normals_have = false;
     std::vector<DepthSlot> dstore;
     mvs::DevBuf fuse_rows, fuse_counts, fuse_scan;  // rows of the last mvs_fuse_depth; per-segment keep counts and their offsets; scan scratch
     bool fuse_have_rows = false;

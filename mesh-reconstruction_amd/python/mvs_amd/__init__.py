@@ -108,6 +108,14 @@ ABI = [
     ("mvs_depth_support_fetch", _i, [_vp, _i, _u8p]),
     ("mvs_depth_support_drop", _i, [_vp, _i]),
     ("mvs_fuse_depth_masked", _i, [_vp, _i, _i, _i32p, _i, _f, _f, _f, _i, _fp, C.POINTER(_i)]),
+    ("mvs_propagate_normals", _i, [_vp, _fp]),
+    ("mvs_propagate_normals_device", _vp, [_vp]),
+    ("mvs_propagate_normals_fetch", _i, [_vp, _fp]),
+    ("mvs_depth_normals_upload", _i, [_vp, _i, _fp]),
+    ("mvs_depth_normals_upload_device", _i, [_vp, _i, _vp]),
+    ("mvs_depth_normals_fetch", _i, [_vp, _i, _fp]),
+    ("mvs_depth_normals_drop", _i, [_vp, _i]),
+    ("mvs_fuse_depth_normals", _i, [_vp, _i, _i, _i32p, _i, _f, _f, _f, _i, _f, _fp, C.POINTER(_i)]),
     ("mvs_tsdf_integrate_masked", _i, [_vp, _i, _i32p, _i32p, _f, _i]),
     ("mvs_fuse_sequence", _i, [_vp, _i, _i32p, _i, _i32p, _i, _f, _f, _f, _i, C.c_longlong, _fp, _i32p, C.POINTER(C.c_longlong)]),
     ("mvs_fuse_sequence_points_device", _vp, [_vp]),
@@ -633,7 +641,7 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
 
 
 def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coarse_planes, z_lo=-1.0, z_hi=1.0, cost=None, propagate=None,
-                        consistency=None, fetch=True, support=False):
+                        consistency=None, fetch=True, support=False, normals=False):
     """Geometric propagation over frames of the frame store: main_slots [n] frame-store slots with their cameras
     main_cams [n,4,4]; side_slots [n,S] and side_cams [n,S,4,4] the side views of each.  The depth store must have 2 n slots
     (Context.depth_store); nothing else is allocated beyond what the calls below allocate.
@@ -645,6 +653,8 @@ def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coars
     are main frames themselves, propagate_init from its own slot i, propagate_run; the z and cost maps go into slot n + i.
     support=True: behind the upload of slot n + i its support map (how many of those neighbours confirm each pixel) goes device to device
     into that slot's support plane (Context.depth_support_upload_device), for fuse_depth / fuse_sequence / tsdf_integrate with min_support.
+    normals=True: behind the upload of slot n + i the frame's normals (Context.propagate_normals of its camera) go
+    device to device into that slot's normal plane, for fuse_depth with min_normal_cos.
     The term (and the gate) are off again on return -> the n stage-2 z maps [n,H,W] float32 (fetch=False: None, they are in the slots).
     WARNING: the neighbours' maps are estimated the same way as the map they correct: consistently wrong neighbours confirm each other,
     and the gain at depth steps is small (section 27 has the figures)."""
@@ -680,6 +690,8 @@ def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coars
             ctx.depth_upload_device(stage * n + i, mc[i], ctx.propagate_depth_pointer(), ctx.propagate_cost_pointer())
             if support and stage == 1:
                 ctx.depth_support_upload_device(n + i, ctx.propagate_support_pointer())
+            if normals and stage == 1:
+                ctx.depth_normals_upload_device(n + i, ctx.propagate_normals(mc[i], fetch=False))
     return out
 
 
@@ -1110,18 +1122,45 @@ class Context:
         """mvs_depth_support_drop: the slot has no support plane any more (its depth map stays)"""
         self._check(self.lib.mvs_depth_support_drop(self.h, int(slot)))
 
+    def depth_normals_upload(self, slot, normals):
+        """mvs_depth_normals_upload: normals [H,W,3] f32 (unit, zeros = none), the normal plane of a filled depth slot (asynchronous: the
+        array is kept alive here until the next fuse_depth / fuse_sequence)"""
+        s = _f32(normals, (self.H, self.W, 3))
+        self.__dict__.setdefault("_depth_keep", {})[("normals", int(slot))] = s
+        self._check(self.lib.mvs_depth_normals_upload(self.h, int(slot), _ptr(s, _fp)))
+
+    def depth_normals_upload_device(self, slot, ptr):
+        """mvs_depth_normals_upload_device: the device address of H*W*3 f32, e.g. propagate_normals_pointer() or tsdf_raycast's normals
+        (stream-ordered)"""
+        self._check(self.lib.mvs_depth_normals_upload_device(self.h, int(slot), C.c_void_p(int(ptr)) if ptr else None))
+
+    def depth_normals_fetch(self, slot):
+        """mvs_depth_normals_fetch -> (H, W, 3) float32, the slot's normal plane; synchronises"""
+        out = np.empty((self.H, self.W, 3), np.float32)
+        self._check(self.lib.mvs_depth_normals_fetch(self.h, int(slot), _ptr(out, _fp)))
+        return out
+
+    def depth_normals_drop(self, slot):
+        """mvs_depth_normals_drop: the slot has no normal plane any more (its depth map stays)"""
+        self._check(self.lib.mvs_depth_normals_drop(self.h, int(slot)))
+
     def fuse_depth(self, ref_slot, neighbour_slots, min_consistent=2, max_reproj_px=1.0, max_rel_depth=0.01, max_cost=float("inf"), copy=True,
-                   min_support=0):
+                   min_support=0, min_normal_cos=None):
         """mvs_fuse_depth -> (N, 7) float32 rows (x, y, z, 1, nx, ny, nz) in ascending pixel index.  copy=False: a view of the context's
         reusable output buffer (the one process_frame uses), valid until the next call that writes it.  min_support > 0:
-        mvs_fuse_depth_masked, rule 1s on the slots' support planes"""
+        mvs_fuse_depth_masked, rule 1s on the slots' support planes.  min_normal_cos a number (<= 1,
+        -inf = no test): mvs_fuse_depth_normals, rules 3n and 5n on the slots' normal planes (section 31)"""
         nb = np.ascontiguousarray(np.asarray(list(neighbour_slots) if len(neighbour_slots) else [0], dtype=np.int32))
         if getattr(self, "_pf_out", None) is None:
             self._pf_out = np.zeros((self.H * self.W, 7), np.float32)
         out = self._pf_out
         n = C.c_int(0)
         try:
-            if int(min_support):
+            if min_normal_cos is not None:
+                self._check(self.lib.mvs_fuse_depth_normals(self.h, int(ref_slot), len(neighbour_slots), _ptr(nb, _i32p), int(min_consistent),
+                                                            float(max_reproj_px), float(max_rel_depth), float(max_cost), int(min_support),
+                                                            float(min_normal_cos), _ptr(out, _fp), C.byref(n)))
+            elif int(min_support):
                 self._check(self.lib.mvs_fuse_depth_masked(self.h, int(ref_slot), len(neighbour_slots), _ptr(nb, _i32p), int(min_consistent),
                                                            float(max_reproj_px), float(max_rel_depth), float(max_cost), int(min_support), _ptr(out, _fp),
                                                            C.byref(n)))
@@ -1558,6 +1597,21 @@ class Context:
     def propagate_support_pointer(self):
         """device address of the support map, H*W uint8 (0 before the first propagate_init)"""
         return self.lib.mvs_propagate_support_device(self.h) or 0
+
+    def propagate_normals(self, cam, fetch=True):
+        """mvs_propagate_normals: world-space unit normals of the hypotheses as they are now, for the main camera cam [4,4] (rule N1,
+        DESIGN.md section 31) -> (H, W, 3) float32, zeros = none; synchronises.  fetch=False: the map's device address (asynchronous)"""
+        c = _f32(cam, (4, 4))
+        self._check(self.lib.mvs_propagate_normals(self.h, _ptr(c, _fp)))
+        if not fetch:
+            return self.propagate_normals_pointer()
+        out = np.empty((self.H, self.W, 3), np.float32)
+        self._check(self.lib.mvs_propagate_normals_fetch(self.h, _ptr(out, _fp)))
+        return out
+
+    def propagate_normals_pointer(self):
+        """device address of the normal map, H*W*3 float32 (0 before the first propagate_normals)"""
+        return self.lib.mvs_propagate_normals_device(self.h) or 0
 
     def propagate_run(self, iterations, dz, dg, nrandom=2, seed=0):
         """mvs_propagate_run: `iterations` PatchMatch iterations on the hypotheses of propagate_init.  In each of an iteration's two
