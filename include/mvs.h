@@ -992,6 +992,62 @@ int mvs_depth_normals_drop(mvs_ctx *ctx, int slot);
 int mvs_fuse_depth_normals(mvs_ctx *ctx, int ref_slot, int nneighbours, const int *neighbour_slots, int min_consistent, float max_reproj_px,
                            float max_rel_depth, float max_cost, int min_support, float min_normal_cos, float *out_points7, int *out_count);
 
+/* ---- depth-map plane fit: gated least-squares slopes, a fitted depth, normals and slope seeds (csrc/depth_fit.hip)
+ * A least-squares plane through the (2 radius + 1)^2 window of every pixel of a depth map, gated like mvs_depth_filter's window: what a
+ * sweep's refined map, a band run's resolved map, a filtered map or a depth-store slot lacks to get normals (their cells hold no slopes),
+ * and a better slope seed for the propagation than MVS_PROPAGATE_SLOPES' one-pixel differences.  All arithmetic is f32 with one rounding
+ * per operation, no contraction and no FMA; sums run in window (row-major) order and start from 0.0f; bit-identical to
+ * tests/depth_fit_mirror.py.
+ *   F1. Valid: -1 < z < 1, read as z + 0.0f (rule 1 of mvs_depth_filter).
+ *   F2. Window and guide gate: rule 2 of mvs_depth_filter; radius 1..4, |G(q) - G(p)| <= tau in integers, tau = 255 reads no guide.
+ *   F3. Members of a valid p: the valid q of the frame that pass the guide gate and whose t(q) = z(q) - z(p) (one rounding) satisfies
+ *       fabsf(t) <= max_step (+inf: no depth gate, 0: equal values only).  p is a member.
+ *   F4. Moments over the members, dc = q.col - p.col, dr = q.row - p.row: n, Sx = sum dc, Sy = sum dr, Sxx, Sxy, Syy exact in int32;
+ *       St = sum t, Sxt = sum (float)dc t, Syt = sum (float)dr t in f32, each product rounded, then added.
+ *   F5. The integer adjugate: A00 = Sxx Syy - Sxy^2, A01 = Sy Sxy - Sx Syy, A02 = Sx Sxy - Sy Sxx, A11 = n Syy - Sy^2,
+ *       A12 = Sx Sy - n Sxy, A22 = n Sxx - Sx^2, D = n A00 + Sx A01 + Sy A02: exact in int32, every |Aij| < 2^24 (exact as a float),
+ *       (float)D one round-to-nearest-even conversion.  p is FITTED when n >= min_members (3..81) and D != 0 (D = 0: the members are
+ *       collinear).  Then c = ((A00 St + A01 Sxt) + A02 Syt) / D, gx = ((A01 St + A11 Sxt) + A12 Syt) / D,
+ *       gy = ((A02 St + A12 Sxt) + A22 Syt) / D, the division correctly rounded.
+ *   F6. Outputs, context-owned: z = z(p) + 0.0f or MVS_BACKGROUND_DEPTH; gx, gy (the depth's change per column and per row, the
+ *       propagation's convention), 0 unless fitted; zfit = z(p) + c when p is fitted and the sum is inside (-1, 1), else z; members = n
+ *       of a fitted pixel, else 0 (u8).  The report: out[0..3] = valid centres, fitted, refused for n < min_members, refused for D = 0.
+ * max_step is in depth units, a few plane steps; the gate keeps the plane from straddling a depth step.  The fit has been measured on
+ * smooth maps with bounded noise and on swept maps: outliers inside the gate pull the plane as they pull a mean.
+ *   depth_dev: every map mvs_depth_filter accepts, and mvs_depth_fit_depth_device itself: a launch never reads the map it writes (an
+ * input that is zfit is fitted into a spare map that is copied over zfit behind the kernel).  guide_dev: H * W u8, NULL = the staged
+ * main image.  mvs_depth_fit_device: z, gx, gy, H * W f32 each, one behind the other, in the layout of mvs_propagate_depth_device;
+ * mvs_depth_fit_depth_device: zfit, a depth map in the library's convention; mvs_depth_fit_members_device: H * W u8.  All are NULL
+ * before the first call and do not change afterwards.  The fetch (each pointer may be NULL) and the report synchronise.  One allocation
+ * (33 H W + 8192 bytes) made by the first mvs_depth_fit behind every check; a context that never calls it allocates nothing.  Asynchronous
+ * on the context's stream, timed under MVS_K_ARGMIN; the call touches no other state.
+ *   mvs_depth_fit_normals: rule N1 (above) on (z, gx, gy) of the last fit for the main camera cam, bit for bit, but a pixel that is not
+ * fitted gets (0, 0, 0) and not the fronto-parallel plane rule N1 gives zero slopes.  mvs_depth_fit_normals_device goes into
+ * mvs_depth_normals_upload_device unchanged (NULL before the first mvs_depth_fit_normals).
+ *   mvs_propagate_set_slopes only records two device pointers (H * W f32 each, e.g. mvs_depth_fit_device + H W and + 2 H W; not the
+ * propagation's own slope maps).  The NEXT mvs_propagate_init that passes its checks consumes them: behind rule 5's copy a pixel with a
+ * hypothesis takes gx(p), gy(p) from them (a non-finite value as 0), a pixel without one keeps 0; then the cells are evaluated as always
+ * and the record is cleared, so the maps must be valid from this call to the end of that init and not longer.  One-shot on purpose: a
+ * later init never reads a map the caller may have freed.  Both NULL clears the record.  Recorded slopes together with
+ * MVS_PROPAGATE_SLOPES are MVS_EINVAL at init (the record stays).  With nothing recorded init writes the bytes it wrote before.
+ * Errors: MVS_EINVAL for a NULL ctx, depth_dev, cam, out or normals array, a radius outside 1..4, tau outside 0..255, a negative or NaN
+ * max_step, min_members outside 3..81, a camera mvs_propagate_normals refuses, gx_dev / gy_dev with only one of them NULL; MVS_ESTATE
+ * for tau < 255 with a NULL guide and no staged main image, for the fetch, the report and mvs_depth_fit_normals before the first fit, for
+ * mvs_depth_fit_normals_fetch before the first mvs_depth_fit_normals; MVS_ENOMEM.  All checks come before the first allocation; after an
+ * error nothing is written and the context stays usable.
+ * Out of scope: a residual-gated refit, hole filling from the fitted plane, normals in mvs_fuse_sequence and TSDF weights from normals,
+ * the exact sampler, the C++ seam (host/recon.hpp). */
+int mvs_depth_fit(mvs_ctx *ctx, const void *depth_dev, const void *guide_dev /* NULL: the staged main image */, int radius, int tau, float max_step, int min_members);
+void *mvs_depth_fit_device(mvs_ctx *ctx);         /* z, gx, gy: 3 * H*W f32 */
+void *mvs_depth_fit_depth_device(mvs_ctx *ctx);   /* zfit: H*W f32 */
+void *mvs_depth_fit_members_device(mvs_ctx *ctx); /* H*W u8 */
+int mvs_depth_fit_fetch(mvs_ctx *ctx, float *z_hw, float *gx_hw, float *gy_hw, float *zfit_hw, uint8_t *members_hw);
+int mvs_depth_fit_report(mvs_ctx *ctx, long long out[4]);
+int mvs_depth_fit_normals(mvs_ctx *ctx, const float cam[16]);
+void *mvs_depth_fit_normals_device(mvs_ctx *ctx); /* H*W*3 f32 */
+int mvs_depth_fit_normals_fetch(mvs_ctx *ctx, float *normals_hw3);
+int mvs_propagate_set_slopes(mvs_ctx *ctx, const void *gx_dev, const void *gy_dev /* both NULL: clear */);
+
 /* ---- one main view on several GPUs of one node (SURVEY.md section 8b "multi-GPU", 8e, north_star) -----------------------------
  * A communicator owns one context per listed device and one RCCL communicator across them (librccl is loaded when the first
  * communicator is created; the library has no link dependency on it).  mvs_sweep_sharded runs ONE main view on all of them, one host

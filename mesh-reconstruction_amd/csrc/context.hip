@@ -277,7 +277,7 @@ void mvs_destroy(mvs_ctx *ctx)
                       &ctx->tsdf_vol, &ctx->tsdf_wmaps, &ctx->tsdf_work, &ctx->tsdf_bricks, &ctx->ray_depth, &ctx->ray_normals, &ctx->agg_cost, &ctx->agg_sum,
                       &ctx->clean_labels, &ctx->clean_sizes, &ctx->clean_counters, &ctx->win_vol, &ctx->band_prior, &ctx->band_depth, &ctx->band_counters,
                       &ctx->tsdf_app, &ctx->shade_map, &ctx->app_points, &ctx->lens_stage, &ctx->pyr_frames, &ctx->filter_density, &ctx->prop_maps, &ctx->prop_counters,
-                      &ctx->dfilter_maps};
+                      &ctx->dfit_maps, &ctx->dfilter_maps};
     for (DevBuf *b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     for (auto &lane : ctx->lanes)

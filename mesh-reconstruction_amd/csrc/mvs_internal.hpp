@@ -249,6 +249,12 @@ struct mvs_ctx {
     // each, one allocation made by the first call; dfilter_have: a call has written the filtered map
     mvs::DevBuf dfilter_maps;
     bool dfilter_have = false;
+    // depth-map plane fit (depth_fit.hip: mvs_depth_fit): z, gx, gy, zfit, a spare map and the normals (8 H*W f32), the report's
+    // 64-bit counters (64 stripes of four) and the members' bytes in one allocation made by the first call; dfit_have: a fit has run, dfit_normals_have:
+    // mvs_depth_fit_normals has.  dfit_seed_gx / _gy: what mvs_propagate_set_slopes recorded for the next mvs_propagate_init (NULL: nothing)
+    mvs::DevBuf dfit_maps;
+    bool dfit_have = false, dfit_normals_have = false;
+    const void *dfit_seed_gx = nullptr, *dfit_seed_gy = nullptr;
     // hypothesis propagation (propagate.hip: mvs_propagate_init / mvs_propagate_run): z, gx, gy (H*W f32 each), the packed cells (H*W u32)
     // and the cost map (H*W f32) in one allocation, and the report's four 64-bit counters, both made by the first init; prop_have: an init
     // has run; what it recorded (cost, radius, keep, the view range) and the iterations run since
@@ -308,6 +314,9 @@ void plane_table(int D, float z_lo, float z_hi, float *z);
 // fuse.hip: the matrices of a depth slot from its camera (P, P^-1 and the centre); false for a camera with a
 // non-finite entry, a singular one, or one without a finite centre.  mvs_tsdf_raycast takes its camera through it too.
 bool slot_matrices(const float cam[16], mvs_ctx::DepthSlot &s);
+// depth_fit.hip: behind mvs_propagate_init's seed kernel, the slope maps mvs_propagate_set_slopes recorded go into gx, gy at the pixels
+// whose z holds a hypothesis, and the record is cleared (nothing recorded: nothing happens)
+void dfit_seed_slopes(mvs_ctx *ctx, const float *z, float *gx, float *gy);
 // tsdf.hip: F and the cell mask of the volume for min_obs into ctx->tsdf_work, unless they are there already (launches on ctx->stream)
 int tsdf_ensure_field(mvs_ctx *ctx, int min_obs);
 // tsdf.hip: the appearance volume, allocated and zeroed unless it is there (ctx->tsdf_app_have)

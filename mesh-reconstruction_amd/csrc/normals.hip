@@ -14,6 +14,7 @@
 // Arithmetic: f32, one rounding per operation, no contraction; tests/normals_mirror.py restates it in numpy.
 #include "fuse_rules.hpp"
 #include "mvs_internal.hpp"
+#include "normals_rules.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -23,12 +24,7 @@ namespace mvs {
 
 namespace {
 
-struct NormalCam {
-    float P[16];  // the main camera, row-major
-    float C[3];   // its centre (slot_matrices)
-};
-
-// rule N1
+// rule N1 (normals_rules.hpp holds its body)
 __global__ __launch_bounds__(256) void hypothesis_normals_kernel(const NormalCam k, const float *__restrict__ zmap, const float *__restrict__ gxmap,
                                                                   const float *__restrict__ gymap, float *__restrict__ out, int W, int H, float invW, float invH,
                                                                   float halfW, float halfH)
@@ -37,26 +33,8 @@ __global__ __launch_bounds__(256) void hypothesis_normals_kernel(const NormalCam
     if (p >= (size_t)W * H) return;
     const int row = (int)(p / W), col = (int)(p - (size_t)row * W);
     const float z = zmap[p], gx = gxmap[p], gy = gymap[p];
-    float nx = 0.f, ny = 0.f, nz = 0.f;
-    if (z > -1.0f && z < 1.0f) {
-        const float xn = __builtin_fmaf((float)(2 * col + 1), invW, -1.0f);
-        const float yn = __builtin_fmaf(-(float)(2 * row + 1), invH, 1.0f);
-        const float a = -gx * halfW, b = gy * halfH;
-        const float d = -((z + a * xn) + b * yn);
-        float m[4];
-        for (int c = 0; c < 4; c++) m[c] = ((a * k.P[c] + b * k.P[4 + c]) + k.P[8 + c]) + d * k.P[12 + c];
-        const float len = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
-        if (len > 0.f && len < INFINITY) {
-            nx = m[0] / len;
-            ny = m[1] / len;
-            nz = m[2] / len;
-            if (((m[0] * k.C[0] + m[1] * k.C[1]) + m[2] * k.C[2]) + m[3] < 0.f) {
-                nx = -nx;
-                ny = -ny;
-                nz = -nz;
-            }
-        }
-    }
+    float nx, ny, nz;
+    rule_n1(k, row, col, z, gx, gy, invW, invH, halfW, halfH, nx, ny, nz);
     out[3 * p] = nx;
     out[3 * p + 1] = ny;
     out[3 * p + 2] = nz;

@@ -430,6 +430,8 @@ int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int 
     if ((rc = bestk_arguments(ctx, who, cost, radius, keep))) return rc;
     if (flags & ~MVS_PROPAGATE_SLOPES) return fail(ctx, MVS_EINVAL, "%s: unknown flag bits 0x%x (MVS_PROPAGATE_SLOPES only)", who, flags & ~MVS_PROPAGATE_SLOPES);
     if (!(max_step >= 0.0f)) return fail(ctx, MVS_EINVAL, "%s: max_step %g is negative or NaN", who, (double)max_step);
+    if ((flags & MVS_PROPAGATE_SLOPES) && ctx->dfit_seed_gx)
+        return fail(ctx, MVS_EINVAL, "%s: MVS_PROPAGATE_SLOPES with recorded slopes (mvs_propagate_set_slopes): one source of slopes only", who);
     if ((rc = staged_state(ctx, who))) return rc;
     if ((rc = fx_sampler_limits(ctx, who, view_first, view_count))) return rc;
     PropGeo tab = {};
@@ -464,6 +466,7 @@ int mvs_propagate_init(mvs_ctx *ctx, const void *depth_dev, int view_first, int 
         ProfileScope ps(ctx, MVS_K_SWEEP);
         const dim3 grid((unsigned)div_up(ctx->W, 32), (unsigned)div_up(ctx->H, 8));
         propagate_seed<<<grid, 256, 0, ctx->stream>>>((const float *)depth_dev, maps, maps + P, maps + 2 * P, ctx->W, ctx->H, (flags & MVS_PROPAGATE_SLOPES) ? 1 : 0, max_step);
+        dfit_seed_slopes(ctx, maps, maps + P, maps + 2 * P);   // section 32: the recorded slope seeds, consumed here
         PropArgs a = {};
         a.half = -1;
         pass(ctx, a);

@@ -167,6 +167,16 @@ ABI = [
     ("mvs_depth_filter", _i, [_vp, _vp, _vp, _i, _i, _f, _i, C.c_uint]),
     ("mvs_depth_filtered_device", _vp, [_vp]),
     ("mvs_depth_filter_fetch", _i, [_vp, _fp]),
+    ("mvs_depth_fit", _i, [_vp, _vp, _vp, _i, _i, _f, _i]),
+    ("mvs_depth_fit_device", _vp, [_vp]),
+    ("mvs_depth_fit_depth_device", _vp, [_vp]),
+    ("mvs_depth_fit_members_device", _vp, [_vp]),
+    ("mvs_depth_fit_fetch", _i, [_vp, _fp, _fp, _fp, _fp, _u8p]),
+    ("mvs_depth_fit_report", _i, [_vp, C.POINTER(C.c_longlong)]),
+    ("mvs_depth_fit_normals", _i, [_vp, _fp]),
+    ("mvs_depth_fit_normals_device", _vp, [_vp]),
+    ("mvs_depth_fit_normals_fetch", _i, [_vp, _fp]),
+    ("mvs_propagate_set_slopes", _i, [_vp, _vp, _vp]),
     ("mvs_propagate_init", _i, [_vp, _vp, _i, _i, _i, _i, _i, _f, C.c_uint]),
     ("mvs_propagate_run", _i, [_vp, _i, _f, _f, _i, C.c_uint]),
     ("mvs_propagate_set_gate", _i, [_vp, _i, _vp]),
@@ -487,9 +497,9 @@ def _propagate_step(ctx, depth_ptr, propagate, cost, step, fetch):
     """the `propagate` keyword of the coarse-to-fine helpers: propagate_init + propagate_run on the map at depth_ptr with the windowed cost
     `cost` = (MVS_COST_*, radius, keep); the random steps are dz_steps / dg_steps plane steps `step` of the level that selected the map
     -> the z map (fetch) or None (it stays at propagate_depth_pointer())"""
-    unknown = set(propagate) - {"iterations", "dz_steps", "dg_steps", "nrandom", "seed", "slopes", "tau", "consistency"}
+    unknown = set(propagate) - {"iterations", "dz_steps", "dg_steps", "nrandom", "seed", "slopes", "tau", "consistency", "fit"}
     if unknown:
-        raise ValueError("propagate: unknown keys %s (iterations, dz_steps, dg_steps, nrandom, seed, slopes, tau, consistency)" % sorted(unknown))
+        raise ValueError("propagate: unknown keys %s (iterations, dz_steps, dg_steps, nrandom, seed, slopes, tau, consistency, fit)" % sorted(unknown))
     if cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
     consistency = propagate.get("consistency")
@@ -497,6 +507,29 @@ def _propagate_step(ctx, depth_ptr, propagate, cost, step, fetch):
         unknown = set(consistency) - {"slots", "weight", "max_px"}
         if unknown:
             raise ValueError("propagate: consistency: unknown keys %s (slots, weight, max_px)" % sorted(unknown))
+    fit = propagate.get("fit")
+    if fit is not None:
+        unknown = set(fit) - {"radius", "tau", "max_steps", "min_members"}
+        if unknown:
+            raise ValueError("propagate: fit: unknown keys %s (radius, tau, max_steps, min_members)" % sorted(unknown))
+        if propagate.get("slopes", False):
+            raise ValueError("propagate: fit with slopes=True: one source of slope seeds only")
+
+    def init():
+        if fit is None:
+            ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
+            return
+        # the plane fit's slopes as seeds: the map is fitted, the depth gate max_steps plane steps of its level, the
+        # slopes are recorded and the init consumes them; a refused init leaves the record, so it is cleared here
+        ctx.depth_fit(depth_ptr, radius=fit.get("radius", 4), tau=fit.get("tau", 255), max_step=float(np.float32(float(fit.get("max_steps", float("inf"))) * step)),
+                      min_members=fit.get("min_members", 6), fetch=False)
+        maps, plane = ctx.depth_fit_pointers()[0], 4 * ctx.W * ctx.H
+        try:
+            ctx.propagate_set_slopes(maps + plane, maps + 2 * plane)
+            ctx.propagate_init(depth_ptr, *cost)
+        finally:
+            ctx.propagate_set_slopes(None, None)
+
     if "tau" in propagate or consistency is not None:
         # the guide gate (the guide the staged main image) and the geometric term (section 27): init takes what is
         # recorded, so the defaults go back at once
@@ -505,14 +538,14 @@ def _propagate_step(ctx, depth_ptr, propagate, cost, step, fetch):
                 ctx.propagate_set_gate(int(propagate["tau"]))
             if consistency is not None:
                 ctx.propagate_set_consistency(**consistency)
-            ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
+            init()
         finally:
             if "tau" in propagate:
                 ctx.propagate_set_gate(255)
             if consistency is not None:
                 ctx.propagate_set_consistency(())
     else:
-        ctx.propagate_init(depth_ptr, *cost, slopes=bool(propagate.get("slopes", False)))
+        init()
     ctx.propagate_run(int(propagate.get("iterations", 3)), float(np.float32(float(propagate.get("dz_steps", 0.5)) * step)),
                       float(np.float32(float(propagate.get("dg_steps", 0.125)) * step)), int(propagate.get("nrandom", 2)), int(propagate.get("seed", 0)))
     return ctx.propagate_fetch()[0] if fetch else None
@@ -544,7 +577,10 @@ def coarse_to_fine(ctx, coarse_planes, band_planes, band_steps=1.5, z_lo=-1.0, z
     26): the gated propagation does repair the edge pixels of a map an ungated sweep made, wherever the step is an intensity edge.
     cost=dict(..., tau=) raises ValueError: the band level has no gate.  The optional key consistency=dict(slots=, weight=, max_px=)
     adds the geometric term against neighbour maps in the depth store (Context.propagate_set_consistency before the init, off again
-    after it; DESIGN.md section 27, with its warning: consistently wrong neighbours confirm each other)."""
+    after it; DESIGN.md section 27, with its warning: consistently wrong neighbours confirm each other).  The optional key
+    fit=dict(radius=4, tau=255, max_steps=inf, min_members=6) seeds the slopes with the plane fit of the start map (Context.depth_fit,
+    the depth gate max_steps plane steps of the band level, then Context.propagate_set_slopes; DESIGN.md section 32) instead of zeros;
+    not together with slopes=True."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     if propagate is not None and cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
@@ -598,7 +634,7 @@ def pyramid_coarse_to_fine(ctxs, coarse_planes, band_planes, band_steps=1.5, z_l
     returned in its place (fetch=False: it stays at ctxs[0].propagate_depth_pointer()).  WARNING, as there: propagation does not help
     beside depth steps, where a window prefers the nearer surface; it spreads that preference -- unless it is gated with the optional
     key tau=, as there.  The optional key consistency=dict(slots=, weight=, max_px=) adds section 27's geometric term on ctxs[0], as
-    there."""
+    there, and the optional key fit=dict(radius=, tau=, max_steps=, min_members=) seeds the slopes with section 32's plane fit, as there."""
     flags = MVS_SWEEP_VOLUME | MVS_SWEEP_FUSED_ARGMIN
     if propagate is not None and cost is None:
         raise ValueError("propagate: needs cost=dict(cost=, radius=, keep=), the windowed cost it evaluates its hypotheses with")
@@ -655,6 +691,8 @@ def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coars
     into that slot's support plane (Context.depth_support_upload_device), for fuse_depth / fuse_sequence / tsdf_integrate with min_support.
     normals=True: behind the upload of slot n + i the frame's normals (Context.propagate_normals of its camera) go
     device to device into that slot's normal plane, for fuse_depth with min_normal_cos.
+    normals="fit": behind the upload of each stage's slot the normals of the plane fit of that stage's final z map (Context.depth_fit with
+    its defaults, then Context.depth_fit_normals of the frame's camera) go into that slot's normal plane instead.
     The term (and the gate) are off again on return -> the n stage-2 z maps [n,H,W] float32 (fetch=False: None, they are in the slots).
     WARNING: the neighbours' maps are estimated the same way as the map they correct: consistently wrong neighbours confirm each other,
     and the gain at depth steps is small (section 27 has the figures)."""
@@ -690,7 +728,11 @@ def propagate_two_stage(ctx, main_slots, main_cams, side_slots, side_cams, coars
             ctx.depth_upload_device(stage * n + i, mc[i], ctx.propagate_depth_pointer(), ctx.propagate_cost_pointer())
             if support and stage == 1:
                 ctx.depth_support_upload_device(n + i, ctx.propagate_support_pointer())
-            if normals and stage == 1:
+            if normals == "fit":
+                # the plane fit of the stage's final z map (section 32): both stages' slots get a plane, unfitted pixels none
+                ctx.depth_fit(ctx.propagate_depth_pointer(), fetch=False)
+                ctx.depth_normals_upload_device(stage * n + i, ctx.depth_fit_normals(mc[i], fetch=False))
+            elif normals and stage == 1:
                 ctx.depth_normals_upload_device(n + i, ctx.propagate_normals(mc[i], fetch=False))
     return out
 
@@ -1555,6 +1597,58 @@ class Context:
     def depth_filtered_pointer(self):
         """device address of the filtered map of the last depth_filter (0 before the first)"""
         return self.lib.mvs_depth_filtered_device(self.h) or 0
+
+    # ---- depth-map plane fit (include/mvs.h, DESIGN.md section 32) --------------------------------
+    def depth_fit(self, depth_ptr, radius=4, tau=255, max_step=float("inf"), min_members=6, guide_ptr=None, fetch=True):
+        """mvs_depth_fit: a least-squares plane through the (2 radius + 1)^2 window of every pixel of the H*W float32 depth map at device
+        address depth_ptr (whatever depth_filter takes, and depth_fit_pointers()[1]).  A neighbour is a member when its guide value is
+        within `tau` of the pixel's (guide_ptr: H*W uint8, None = the staged main image; tau 255 = no guide) and its depth within
+        max_step of the pixel's (inf = no depth gate); a pixel is fitted when it has at least min_members (3..81) members that are not
+        collinear.  fetch: -> (z, gx, gy, zfit (H, W) float32, members (H, W) uint8): the map as read, the depth's change per column and
+        per row (0 unless fitted), the depth moved onto the plane, and the members of a fitted pixel (else 0); synchronises.  Else None
+        (asynchronous, stream-ordered; the maps stay at depth_fit_pointers())"""
+        self._check(self.lib.mvs_depth_fit(self.h, C.c_void_p(int(depth_ptr)) if depth_ptr else None, C.c_void_p(int(guide_ptr)) if guide_ptr else None,
+                                           int(radius), int(tau), float(max_step), int(min_members)))
+        if not fetch:
+            return None
+        z, gx, gy, zfit = (np.empty((self.H, self.W), np.float32) for _ in range(4))
+        members = np.empty((self.H, self.W), np.uint8)
+        self._check(self.lib.mvs_depth_fit_fetch(self.h, _ptr(z, _fp), _ptr(gx, _fp), _ptr(gy, _fp), _ptr(zfit, _fp), _ptr(members, _u8p)))
+        return z, gx, gy, zfit, members
+
+    def depth_fit_pointers(self):
+        """device addresses (z, gx, gy: 3 * H*W float32 in propagate_depth_pointer()'s layout; zfit H*W float32, a depth map; members
+        H*W uint8) of the last depth_fit; (0, 0, 0) before the first"""
+        return self.lib.mvs_depth_fit_device(self.h) or 0, self.lib.mvs_depth_fit_depth_device(self.h) or 0, self.lib.mvs_depth_fit_members_device(self.h) or 0
+
+    def depth_fit_report(self):
+        """mvs_depth_fit_report -> [valid centres, fitted, refused for too few members, refused for collinear members] of the last
+        depth_fit; synchronises"""
+        out = (C.c_longlong * 4)()
+        self._check(self.lib.mvs_depth_fit_report(self.h, out))
+        return list(out)
+
+    def depth_fit_normals(self, cam, fetch=True):
+        """mvs_depth_fit_normals: world-space unit normals of the last depth_fit's planes for the main camera cam [4,4] (rule N1, DESIGN.md
+        section 31; a pixel that is not fitted gets zeros) -> (H, W, 3) float32; synchronises.  fetch=False: the map's device address
+        (asynchronous), which depth_normals_upload_device takes"""
+        c = _f32(cam, (4, 4))
+        self._check(self.lib.mvs_depth_fit_normals(self.h, _ptr(c, _fp)))
+        if not fetch:
+            return self.depth_fit_normals_pointer()
+        out = np.empty((self.H, self.W, 3), np.float32)
+        self._check(self.lib.mvs_depth_fit_normals_fetch(self.h, _ptr(out, _fp)))
+        return out
+
+    def depth_fit_normals_pointer(self):
+        """device address of the fit's normal map, H*W*3 float32 (0 before the first depth_fit_normals)"""
+        return self.lib.mvs_depth_fit_normals_device(self.h) or 0
+
+    def propagate_set_slopes(self, gx_ptr, gy_ptr):
+        """mvs_propagate_set_slopes: records two device addresses of H*W float32 slope maps (e.g. depth_fit_pointers()[0] + 4 H W and
+        + 8 H W) that the NEXT propagate_init which passes its checks gives to the pixels with a hypothesis in place of zero slopes (a
+        non-finite value as 0), and forgets: one-shot.  (None, None) clears the record.  Not together with propagate_init(slopes=True)"""
+        self._check(self.lib.mvs_propagate_set_slopes(self.h, C.c_void_p(int(gx_ptr)) if gx_ptr else None, C.c_void_p(int(gy_ptr)) if gy_ptr else None))
 
     # ---- hypothesis propagation (include/mvs.h, DESIGN.md section 25) ----------------------------
     def propagate_init(self, depth_ptr, cost, radius=2, keep=MVS_KEEP_ALL, view_first=0, view_count=None, slopes=False, max_step=float("inf")):
